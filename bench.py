@@ -2,6 +2,12 @@
 """DeepFM Criteo-shaped train-step throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model deepfm|dcnv2|din]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line;
+--dump-outputs DIR also writes what the last timed step computed (dump_outputs).
+--full adds the measurements that take runs of their own: the per-kernel roofline,
+the PCIe-inclusive (host-fed) rate and the CPU baseline.
 
 One step = one full training step (interact fwd -> MLP fwd -> head + BCE ->
 MLP bwd -> embedding sorted-segment backward, with SGD fused into every
@@ -55,6 +61,15 @@ def parse(argv=None):
     p.add_argument("--graph-steps", type=int, default=4,
                    help="consecutive train steps (one per resident batch) captured in one HIP "
                         "graph: one graph launch per G steps instead of per step")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure what takes runs of its own: the "
+                        "per-kernel roofline, the PCIe-inclusive (host-fed) rate and the CPU "
+                        "baseline (each still switched off by its --no-* option); a plain run "
+                        "only sets up, warms up, times the steps and prints the result line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step computed (its "
+                        "loss and the parameters it updated; a fixed seeded sample of the rows "
+                        "of a large tensor) as DIR/<name>.npy, float32")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=12.0)
     p.add_argument("--no-roofline", action="store_true")
@@ -86,6 +101,8 @@ def parse(argv=None):
     if args.rows_per_table is None:
         # N = 1: C2 (~1M rows); N > 1: C5, 100M-row tables row-sharded over the ranks
         args.rows_per_table = C5_ROWS if args.gpus > 1 else CRITEO_ROWS
+    if not args.full:  # a plain run: the headline figure only
+        args.no_roofline = args.no_h2d = args.no_cpu_baseline = True
     return args
 
 
@@ -1134,6 +1151,7 @@ def main():
         return model.train_step(d)["loss"]
 
     graphs = None
+    last = [None]  # the loss tensor the last step run wrote (--dump-outputs)
     if not args.no_graph:
         # one graph per resident batch (inputs used in place: no staging copy)
         s = torch.cuda.Stream()
@@ -1143,11 +1161,11 @@ def main():
                 step(datas[k % 4])
         torch.cuda.current_stream().wait_stream(s)
         try:
-            graphs = []
+            graphs, losses = [], []  # (a captured step's loss stays allocated while held)
             for d in datas:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    step(d)
+                    losses.append(step(d))
                 graphs.append(g)
             multi = None
             G = max(1, min(args.graph_steps, 4))
@@ -1155,7 +1173,7 @@ def main():
                 multi = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(multi, capture_error_mode="thread_local"):
                     for k in range(G):
-                        step(datas[k])
+                        multi_loss = step(datas[k])
         except Exception as e:  # e.g. a collective the runtime cannot capture
             print(f"bench: HIP graph capture failed ({type(e).__name__}: {e}); running eagerly",
                   file=sys.stderr, flush=True)
@@ -1165,9 +1183,10 @@ def main():
 
     def run(i):
         if graphs is None:
-            step(datas[i % 4])
+            last[0] = step(datas[i % 4])
         else:
             graphs[i % 4].replay()
+            last[0] = losses[i % 4]
 
     def run_steps(n):
         """n train steps, batch i % 4 at step i: G-step graphs while n allows, then
@@ -1176,6 +1195,7 @@ def main():
         if graphs is not None and multi is not None:
             while n - i >= G:
                 multi.replay()
+                last[0] = multi_loss
                 i += G
         while i < n:
             run(i)
@@ -1199,6 +1219,8 @@ def main():
     for b in model.embedding_banks():
         if isinstance(b, ShardedEmbeddingBank) and os.environ.get("MREC_BENCH_DIAG_NOCHECK") != "1":
             b.check_flags()  # an exchange overflow would make the run invalid: raise
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, last[0])
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -1321,6 +1343,43 @@ def main():
               flush=True)
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
+
+
+DUMP_TENSOR_BYTES = 8 << 20  # per file; larger tensors are sampled
+DUMP_TOTAL_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, loss):
+    """--dump-outputs: what the last timed train step handed its caller, as float32
+    ``<name>.npy`` files: ``loss`` (the step's return value) and every parameter as
+    the step's fused updates left it (``param.<name>``; at N > 1 rank 0's shard).
+    A tensor above DUMP_TENSOR_BYTES is sampled: rows (elements of a 1-D tensor)
+    drawn once with a fixed seed, so two runs with the same arguments write the
+    same rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    total = 0
+
+    def save(name, t):
+        nonlocal total
+        t = t.detach()
+        if t.dim() == 0:
+            t = t.reshape(1)
+        row = max(1, t.numel() // max(1, t.shape[0])) * 4
+        keep = min(DUMP_TENSOR_BYTES, DUMP_TOTAL_BYTES - total) // row
+        if t.shape[0] > keep:
+            rng = np.random.default_rng(2020)
+            idx = np.unique(rng.integers(0, t.shape[0], size=keep))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = t.float().cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+    if loss is not None:
+        save("loss", loss)
+    for name, p in model.named_parameters():
+        save("param." + name, p)
 
 
 def _exchange_desc(model, args):

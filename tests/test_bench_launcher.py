@@ -38,6 +38,17 @@ def test_launcher_single_gpu_unchanged():
     assert d["n_gpus"] == 1 and d["config"]["rows_per_table"] == 38462  # C2
 
 
+def test_plain_run_measures_the_headline_only():
+    """Without --full the roofline, the host-fed leg and the CPU baseline are off;
+    with it each stays under its own --no-* switch."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert a.no_roofline and a.no_h2d and a.no_cpu_baseline and a.dump_outputs is None
+    a = bench.parse(["--full", "--no-h2d", "--dump-outputs", "d"])
+    assert not a.no_roofline and a.no_h2d and not a.no_cpu_baseline and a.dump_outputs == "d"
+
+
 def test_launcher_refuses_mismatched_world():
     p = _bench("--gpus", "1", "--stub-step", env={"WORLD_SIZE": "2", "RANK": "0"})
     assert p.returncode != 0 and "WORLD_SIZE=2" in p.stderr

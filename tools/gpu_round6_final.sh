@@ -10,8 +10,8 @@ export TMPDIR=/tmp
 o=$GRAFT_REPO_ROOT/gpurun_out/${OUT:-final6}
 mkdir -p $o
 cd $GRAFT_REPO_ROOT
-plain() { name=$1; shift; timeout -k 10 400 python3 bench.py "$@" > $o/$name.json 2> $o/$name.err || { tail -5 $o/$name.err; exit 1; }; python3 -c "import json; d=json.load(open('$o/$name.json')); r=d['roofline']; print('$name', d['ms_per_step'], d['value'], r.get('frac'), r.get('traffic'))"; }
-prof() { name=$1; shift; (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $o/$name -o run -- python3 $GRAFT_REPO_ROOT/bench.py "$@" > $o/$name.json 2> $o/$name.err) || { tail -5 $o/$name.err; exit 1; }; python3 -c "import json; d=json.load(open('$o/$name.json')); print('$name', d['ms_per_step'])"; }
+plain() { name=$1; shift; timeout -k 10 400 python3 bench.py --full "$@" > $o/$name.json 2> $o/$name.err || { tail -5 $o/$name.err; exit 1; }; python3 -c "import json; d=json.load(open('$o/$name.json')); r=d['roofline']; print('$name', d['ms_per_step'], d['value'], r.get('frac'), r.get('traffic'))"; }
+prof() { name=$1; shift; (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $o/$name -o run -- python3 $OLDPWD/bench.py --full "$@" > $o/$name.json 2> $o/$name.err) || { tail -5 $o/$name.err; exit 1; }; python3 -c "import json; d=json.load(open('$o/$name.json')); print('$name', d['ms_per_step'])"; }
 if [ "${PHASE:-A}" = A ]; then
   timeout -k 10 900 python3 -u -m pytest tests -m gpu -q --timeout 120 --timeout-method thread > $o/pytest.log 2>&1 || { tail -30 $o/pytest.log; exit 1; }
   tail -2 $o/pytest.log

@@ -10,8 +10,8 @@ timeout -k 10 900 python3 -u -m pytest tests -m gpu -q --timeout 120 --timeout-m
 tail -2 $o/pytest.log
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $o/smoke.log 2>&1 || { tail -5 $o/smoke.log; exit 1; }
 tail -1 $o/smoke.log
-plain() { name=$1; shift; timeout -k 10 400 python3 bench.py "$@" > $o/$name.json 2> $o/$name.err || { tail -5 $o/$name.err; exit 1; }; python3 -c "import json; d=json.load(open('$o/$name.json')); print('$name', d['ms_per_step'], d['value'])"; }
-prof() { name=$1; shift; (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $o/$name -o run -- python3 $GRAFT_REPO_ROOT/bench.py "$@" > $o/$name.json 2> $o/$name.err) || { tail -5 $o/$name.err; exit 1; }; python3 -c "import json; d=json.load(open('$o/$name.json')); print('$name', d['ms_per_step'])"; }
+plain() { name=$1; shift; timeout -k 10 400 python3 bench.py --full "$@" > $o/$name.json 2> $o/$name.err || { tail -5 $o/$name.err; exit 1; }; python3 -c "import json; d=json.load(open('$o/$name.json')); print('$name', d['ms_per_step'], d['value'])"; }
+prof() { name=$1; shift; (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $o/$name -o run -- python3 $OLDPWD/bench.py --full "$@" > $o/$name.json 2> $o/$name.err) || { tail -5 $o/$name.err; exit 1; }; python3 -c "import json; d=json.load(open('$o/$name.json')); print('$name', d['ms_per_step'])"; }
 plain bench_deepfm_c2 && plain bench_dcnv2_c3 --model dcnv2 --no-cpu-baseline && plain bench_din_c4 --model din --no-cpu-baseline \
   && plain bench_deepfm_c2_zipf --zipf 1.05 --no-cpu-baseline --no-h2d \
   && plain bench_shard_w1_compact --shard --force-collectives --exchange compact --no-cpu-baseline --no-h2d \
