@@ -76,9 +76,7 @@ struct KcScope<true> {
   __device__ KcScope(const KClock &k, int c) : kc(k), t0(__builtin_amdgcn_s_memrealtime()), cat(c) {}
   __device__ ~KcScope() {
     if ((threadIdx.x & 63) == 0) {
-#ifndef MREC_KC_NOWAIT  // (diagnostic: stamp at the last issue, not the last acknowledgement)
-      __builtin_amdgcn_s_waitcnt(0);
-#endif
+      __builtin_amdgcn_s_waitcnt(0);  // stamp at the last acknowledgement, not the last issue
       const unsigned wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
       const unsigned shard = cat < 0 ? wave % MREC_KCLOCK_SHARDS : cat * 1024 + (wave & 1023);
       unsigned long long *p =

@@ -3,7 +3,7 @@
 // One workgroup (8 waves) per sample b at a time, persistent over samples.  The
 // attention-unit input X = [q | k_j | q - k_j | q * k_j] (64 padded history rows x
 // 4E), the MLP activations and every gradient live in LDS only; the MLP weights
-// are staged once per workgroup as bf16 in both operand orders.  What the layered
+// are staged once per workgroup as bf16.  What the layered
 // path (mrec_din_feat_fwd + three mrec_gemm layers + mrec_din_pool_*) moved
 // through HBM per step at C4 -- the [B L, 128] input, the [B L, 80] / [B L, 40]
 // activations and their gradients, ~0.4 GB -- never leaves the CU.
@@ -23,8 +23,8 @@
 // All GEMMs are v_mfma_f32_16x16x32_bf16 with both operands read as 16-B LDS
 // vectors: lane l holds A[m = l % 16][k = 8 (l / 16) .. + 8] and the B^T row
 // B[k .. + 8][n = l % 16]; so every operand buffer is stored "row = output index,
-// contiguous along k" and the reductions over history rows read transposed copies
-// ([feature][row]) written beside the row-major ones.
+// contiguous along k" and the reductions over history rows read the row-major
+// buffers transposed (da_frag_tr).
 #include <cstdlib>
 
 #include "common.h"
@@ -37,7 +37,6 @@ typedef float da_f32x4 __attribute__((ext_vector_type(4)));
 constexpr int DA_ROWS = 64;              // history positions per sample, padded
 constexpr int DA_CG = 2;                 // column groups: 8 waves = 4 row tiles x 2
 constexpr int DA_THREADS = 64 * 4 * DA_CG;
-constexpr int DA_LDT = DA_ROWS + 8;      // row stride of the [feature][row] buffers
 
 struct DinAttArgs {
   const uint16_t *rows;  // gathered rows [q (batch) | k (batch L)] bf16
@@ -99,29 +98,16 @@ struct DaShape {
   static constexpr int LDH = H1P + 8;
   static constexpr int H2N = 16 * H2T;
   static constexpr int H2P = 32 * H2K;
-  static constexpr int LDW2T = H2P + 8;
   static_assert(E % 16 == 0 && E4 % 32 == 0, "E must be a multiple of 16");
   static_assert(H1N <= H1P && H2N <= H2P, "k-step padding covers the tiles");
-  static_assert(H2P <= H1P, "dZ2 aliases H1 with H1's row stride");
-  static_assert(H1P <= E4, "dZ1 aliases X");
   // bf16 element offsets of the LDS buffers (16-B aligned: every size % 8 == 0)
-  static constexpr int oX = 0;                       // X [64][LDX]   (bwd: dZ1 [64][LDH])
-  static constexpr int oH1 = oX + DA_ROWS * LDX;     // H1 [64][LDH]  (bwd: dZ2 [64][LDH])
+  static constexpr int oX = 0;                       // X [64][LDX]
+  static constexpr int oH1 = oX + DA_ROWS * LDX;     // H1 [64][LDH]
   static constexpr int oW1 = oH1 + DA_ROWS * LDH;    // W1 [H1N][LDX]
   static constexpr int oW2 = oW1 + H1N * LDX;        // W2 [H2N][LDH]
   static constexpr int fwd_end = oW2 + H2N * LDH;
-  static constexpr int oXT = fwd_end;                // X^T [E4][LDT]
-  static constexpr int oH1T = oXT + E4 * DA_LDT;     // H1^T [H1N][LDT]
-  static constexpr int oZ1T = oH1T + H1N * DA_LDT;   // dZ1^T [H1N][LDT]
-  static constexpr int oZ2T = oZ1T + H1N * DA_LDT;   // dZ2^T [H2N][LDT]
-  static constexpr int oW1T = oZ2T + H2N * DA_LDT;   // W1^T [E4][LDH]
-  static constexpr int oW2T = oW1T + E4 * LDH;       // W2^T [H1N][LDW2T]
-  static constexpr int bwd_end = oW2T + H1N * LDW2T;
-  // fp32 tail: b1 [H1N], b2 [H2N], w3 [H2N], q [E], du [E], g [64], dq parts [4][E]
-  static constexpr int nf32 = H1N + 2 * H2N + 2 * E + DA_ROWS + 4 * E;
   static constexpr size_t fwd_bytes =
       fwd_end * 2 + (H1N + 2 * H2N + (DA_CG + 1) * DA_ROWS + DA_THREADS) * 4;
-  static constexpr size_t bwd_bytes = bwd_end * 2 + nf32 * 4;
 };
 
 __device__ __forceinline__ void da_zero_lds(char *lds, size_t bytes) {
@@ -132,7 +118,7 @@ __device__ __forceinline__ void da_zero_lds(char *lds, size_t bytes) {
 // Weights once per workgroup: every float4 load of a thread is issued before any
 // is converted (a load -> store loop of ~55 dependent L2 round trips per thread
 // cost ~40 us per launch).  Needs ldw1, ldw2, H1 multiples of 4, 16-B aligned w1 / w2.
-template <class S, bool BWD>
+template <class S>
 __device__ void da_stage_weights(const DinAttArgs &p, uint16_t *sm, float *sb1, float *sb2,
                                  float *sw3) {
   const int tid = threadIdx.x;
@@ -170,10 +156,6 @@ __device__ void da_stage_weights(const DinAttArgs &p, uint16_t *sm, float *sb1, 
     *reinterpret_cast<uint2 *>(sm + S::oW1 + n * S::LDX + k) =
         make_uint2(h[0] | (static_cast<uint32_t>(h[1]) << 16),
                    h[2] | (static_cast<uint32_t>(h[3]) << 16));
-    if constexpr (BWD) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) sm[S::oW1T + (k + c) * S::LDH + n] = h[c];
-    }
   }
   DA_STAMP(62);
 #pragma unroll
@@ -186,10 +168,6 @@ __device__ void da_stage_weights(const DinAttArgs &p, uint16_t *sm, float *sb1, 
     *reinterpret_cast<uint2 *>(sm + S::oW2 + n * S::LDH + k) =
         make_uint2(h[0] | (static_cast<uint32_t>(h[1]) << 16),
                    h[2] | (static_cast<uint32_t>(h[3]) << 16));
-    if constexpr (BWD) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) sm[S::oW2T + (k + c) * S::LDW2T + n] = h[c];
-    }
   }
 }
 
@@ -234,7 +212,7 @@ __device__ __forceinline__ DaRaw da_load(const DinAttArgs &p, int64_t b, const D
 
 // X row j of sample b: [q | k | q - k | q * k] as bf16 (the rounding of
 // din_feat_fwd_kernel); rows j >= L are zero.  Returns k (fp32) and q (fp32).
-template <class S, int E, bool TR>
+template <class S, int E>
 __device__ __forceinline__ void da_build_x(const DinAttArgs &p, const DaRaw &raw,
                                            const DaTask<E> &t, uint16_t *sm, float (&qv)[8],
                                            float (&kv)[8]) {
@@ -259,17 +237,6 @@ __device__ __forceinline__ void da_build_x(const DinAttArgs &p, const DaRaw &raw
   *reinterpret_cast<uint4 *>(x + E) = kraw;
   *reinterpret_cast<uint4 *>(x + 2 * E) = dq;
   *reinterpret_cast<uint4 *>(x + 3 * E) = mq;
-  if constexpr (TR) {
-    uint16_t *xt = sm + S::oXT + t.c * DA_LDT + t.j;
-    const uint4 parts[4] = {qq, kraw, dq, mq};
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const uint32_t u[4] = {parts[g].x, parts[g].y, parts[g].z, parts[g].w};
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        xt[(g * E + i) * DA_LDT] = static_cast<uint16_t>(u[i >> 1] >> (16 * (i & 1)));
-    }
-  }
 }
 
 // Wave w = (row tile rt = w / 2: rows 16 rt .. + 15, column group cg = w % 2; the
@@ -331,7 +298,7 @@ __global__ __launch_bounds__(DA_THREADS) void din_att_fwd_kernel(DinAttArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, rt = w >> 1, cg = w & 1;
   da_zero_lds(da_lds, S::fwd_end * 2);
   __syncthreads();
-  da_stage_weights<S, false>(p, sm, sb1, sb2, sw3);
+  da_stage_weights<S>(p, sm, sb1, sb2, sw3);
   const float b3 = p.b3[0];
   const DaTask<E> task(tid);
   DaRaw cur = {};
@@ -339,7 +306,7 @@ __global__ __launch_bounds__(DA_THREADS) void din_att_fwd_kernel(DinAttArgs p) {
   for (int64_t b = blockIdx.x; b < p.batch; b += gridDim.x) {
     if (task.on) {
       float qv[8], kv[8];
-      da_build_x<S, E, false>(p, cur, task, sm, qv, kv);
+      da_build_x<S, E>(p, cur, task, sm, qv, kv);
     }
     // rows past the last valid history position only feed masked scores: their
     // row tiles skip the MLP (wave-uniform: every wave holds all 64 validity bits)
@@ -530,7 +497,7 @@ __global__ __launch_bounds__(DA_THREADS, 1) void din_att_fwd_wave_kernel(DinAttA
     *reinterpret_cast<uint4 *>(ws + o) = make_uint4(0, 0, 0, 0);
   __syncthreads();
   DA_STAMP(60);
-  da_stage_weights<S, false>(p, sm, sb1, sb2, sw3);
+  da_stage_weights<S>(p, sm, sb1, sb2, sw3);
   __syncthreads();
   DA_STAMP(1);
   // layer 1's B fragments in VGPRs (80 at C4); layer 2's are read from the staged
@@ -689,316 +656,6 @@ __global__ __launch_bounds__(DA_THREADS, 1) void din_att_fwd_wave_kernel(DinAttA
 }
 
 // ---------------------------------------------------------------------------
-// backward: pooling backward, MLP recomputed + back-propagated, dX -> d rows,
-// weight-gradient partials per workgroup
-// ---------------------------------------------------------------------------
-template <int E, int H1T, int H1K, int H2T, int H2K>
-__global__ __launch_bounds__(DA_THREADS) void din_att_bwd_kernel(DinAttArgs p) {
-  using S = DaShape<E, H1T, H1K, H2T, H2K>;
-  constexpr int NTX = S::NTX;
-  constexpr int EC = E / 16;  // column tiles per block of X
-  constexpr int J1 = (H1T + DA_CG - 1) / DA_CG, J2 = (H2T + DA_CG - 1) / DA_CG;
-  constexpr int JX = (EC + DA_CG - 1) / DA_CG;
-  constexpr int NWV = DA_THREADS / 64;
-  constexpr int NW1 = (H1T * NTX + NWV - 1) / NWV;  // dW1 tiles per wave
-  constexpr int NW2 = (H2T * H1T + NWV - 1) / NWV;  // dW2 tiles per wave
-  extern __shared__ __attribute__((aligned(16))) char da_lds[];
-  uint16_t *sm = reinterpret_cast<uint16_t *>(da_lds);
-  float *sb1 = reinterpret_cast<float *>(da_lds + S::bwd_end * 2);
-  float *sb2 = sb1 + S::H1N;
-  float *sw3 = sb2 + S::H2N;
-  float *sq = sw3 + S::H2N;  // q [E] fp32
-  float *sdu = sq + E;       // du = dtop[b, E:2E] [E]
-  float *sg = sdu + E;       // g_j = du . k_j [64]
-  float *sdq = sg + DA_ROWS;  // per-row-tile dq parts [4][E]
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, rt = w >> 1, cg = w & 1;
-  DA_STAMP(0);
-  da_zero_lds(da_lds, S::bwd_end * 2);
-  __syncthreads();
-  da_stage_weights<S, true>(p, sm, sb1, sb2, sw3);
-  const DaTask<E> task(tid);
-  int sidx = 0;
-  DA_STAMP(1);
-
-  da_f32x4 gw1[NW1], gw2[NW2];
-#pragma unroll
-  for (int i = 0; i < NW1; ++i) gw1[i] = da_f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int i = 0; i < NW2; ++i) gw2[i] = da_f32x4{0.f, 0.f, 0.f, 0.f};
-  float gb1[J1], gb2[J2], gw3[J2];  // per-lane column partials (column 16 n + lane % 16)
-#pragma unroll
-  for (int n = 0; n < J1; ++n) gb1[n] = 0.f;
-#pragma unroll
-  for (int n = 0; n < J2; ++n) gb2[n] = gw3[n] = 0.f;
-  float gb3 = 0.f;
-
-  DaRaw cur = {};
-  if (blockIdx.x < p.batch) cur = da_load<E, true>(p, blockIdx.x, task, lane);
-  for (int64_t b = blockIdx.x; b < p.batch; b += gridDim.x) {
-    DaRaw nxt = {};
-    if (b + gridDim.x < p.batch) nxt = da_load<E, true>(p, b + gridDim.x, task, lane);
-    // ---- phase 0: X / X^T, q, du, g_j = du . k_j ----
-    if (task.on) {
-      float qv[8], kv[8], dv[8];
-      da_build_x<S, E, true>(p, cur, task, sm, qv, kv);
-      Vec<uint16_t>::to_f32(cur.du, dv);
-      float g = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) g = fmaf(dv[i], kv[i], g);
-#pragma unroll
-      for (int off = 1; off < DaTask<E>::CH; off <<= 1) g += __shfl_xor(g, off);
-      if (task.c == 0) sg[task.j] = g;
-      if (task.j == 0) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          sq[task.c + i] = qv[i];
-          sdu[task.c + i] = dv[i];
-        }
-      }
-    }
-    const float aj = cur.a;  // lane = history row
-    // rows past the last one with a_j != 0 have ds = 0, dX = 0 and add nothing to the
-    // weight gradients: their row tiles skip every MFMA (accumulators stay 0, so the
-    // epilogues store the same zeros), and the dW k steps past them are skipped
-    const uint64_t am = __ballot(aj != 0.f);
-    const int nv = am ? 64 - __clzll(am) : 0;
-    const bool act = 16 * rt < nv;
-    const int kk = nv > 32 ? 2 : 1;
-    __syncthreads();
-    DA_STAMP(2 + 8 * sidx + 0);
-    // ---- phase 1: ds (every wave, lane = row), layer 1 -> H1, H1^T ----
-    const float gj = sg[lane];
-    const float ag = sum_wave(aj * gj);
-    const float dsj = aj * (gj - ag);
-    if (w == 0) gb3 += sum_wave(dsj);  // lane 0's value is written
-    {
-      da_f32x4 acc[J1];
-      da_layer1<S, H1T>(sm, rt, cg, lane, act, acc);
-#pragma unroll
-      for (int jn = 0; jn < J1; ++jn) {
-        const int n = cg + DA_CG * jn;
-        if (n >= H1T) continue;
-        const int col = 16 * n + (lane & 15);
-        const float bias = sb1[col];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int r = 16 * rt + 4 * (lane >> 4) + i;
-          const uint16_t h = f32_to_bf16_rne(fmaxf(acc[jn][i] + bias, 0.f));
-          sm[S::oH1 + r * S::LDH + col] = h;
-          sm[S::oH1T + col * DA_LDT + r] = h;
-        }
-      }
-    }
-    __syncthreads();
-    DA_STAMP(2 + 8 * sidx + 1);
-    // ---- phase 2: layer 2, dZ2 = ds w3 relu'(z2) -> dZ2 (over H1), dZ2^T ----
-    {
-      da_f32x4 acc[J2];
-      da_layer2<S, H1K, H2T>(sm, rt, cg, lane, act, acc);
-      __syncthreads();  // both column groups' reads of these H1 rows precede the dZ2 stores
-#pragma unroll
-      for (int jn = 0; jn < J2; ++jn) {
-        const int n = cg + DA_CG * jn;
-        if (n >= H2T) continue;
-        const int col = 16 * n + (lane & 15);
-        const float bias = sb2[col], wv = sw3[col];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int r = 16 * rt + 4 * (lane >> 4) + i;
-          const float dsr = __shfl(dsj, r);
-          const float h2 = fmaxf(acc[jn][i] + bias, 0.f);
-          const float dz = h2 > 0.f ? dsr * wv : 0.f;
-          gw3[jn] = fmaf(dsr, h2, gw3[jn]);
-          gb2[jn] += dz;
-          const uint16_t hz = f32_to_bf16_rne(dz);
-          sm[S::oH1 + r * S::LDH + col] = hz;
-          sm[S::oZ2T + col * DA_LDT + r] = hz;
-        }
-      }
-    }
-    __syncthreads();
-    DA_STAMP(2 + 8 * sidx + 2);
-    // ---- phase 3: dH1 = dZ2 W2, dZ1 = dH1 relu'(H1) -> dZ1 (over X), dZ1^T; dW2 ----
-    {
-      da_f32x4 acc[J1];
-#pragma unroll
-      for (int jn = 0; jn < J1; ++jn) acc[jn] = da_f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < H2K; ++s) {
-        if (!act) break;
-        const da_bf16x8 a = da_frag(sm + S::oH1, S::LDH, 16 * rt, 32 * s, lane);
-#pragma unroll
-        for (int jn = 0; jn < J1; ++jn) {
-          const int n = cg + DA_CG * jn;
-          if (n < H1T)
-            acc[jn] = da_mfma(a, da_frag(sm + S::oW2T, S::LDW2T, 16 * n, 32 * s, lane), acc[jn]);
-        }
-      }
-#pragma unroll
-      for (int jn = 0; jn < J1; ++jn) {
-        const int n = cg + DA_CG * jn;
-        if (n >= H1T) continue;
-        const int col = 16 * n + (lane & 15);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int r = 16 * rt + 4 * (lane >> 4) + i;
-          const uint16_t h = sm[S::oH1T + col * DA_LDT + r];
-          const float dz = (h != 0 && !(h & 0x8000u)) ? acc[jn][i] : 0.f;
-          gb1[jn] += dz;
-          const uint16_t hz = f32_to_bf16_rne(dz);
-          sm[S::oX + r * S::LDH + col] = hz;  // dZ1 over X (dead since phase 1)
-          sm[S::oZ1T + col * DA_LDT + r] = hz;
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < NW2; ++i) {
-        const int t = w + NWV * i;
-        if (t < H2T * H1T) {
-          const int m = t / H1T, n = t - m * H1T;
-#pragma unroll
-          for (int s = 0; s < 2; ++s)
-            if (s < kk)
-            gw2[i] = da_mfma(da_frag(sm + S::oZ2T, DA_LDT, 16 * m, 32 * s, lane),
-                             da_frag(sm + S::oH1T, DA_LDT, 16 * n, 32 * s, lane), gw2[i]);
-        }
-      }
-    }
-    __syncthreads();
-    DA_STAMP(2 + 8 * sidx + 3);
-    // ---- phase 4: dX = dZ1 W1 -> d rows (dk per row, dq parts); dW1 ----
-    {
-      // the wave's X column tiles: blocks q / k / q-k / q*k of column tiles c16 = cg + DA_CG jx
-      da_f32x4 acc[JX][4];
-#pragma unroll
-      for (int jx = 0; jx < JX; ++jx)
-#pragma unroll
-        for (int blk = 0; blk < 4; ++blk) acc[jx][blk] = da_f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < H1K; ++s) {
-        if (!act) break;
-        const da_bf16x8 a = da_frag(sm + S::oX, S::LDH, 16 * rt, 32 * s, lane);
-#pragma unroll
-        for (int jx = 0; jx < JX; ++jx) {
-          const int c16 = cg + DA_CG * jx;
-          if (c16 >= EC) continue;
-#pragma unroll
-          for (int blk = 0; blk < 4; ++blk)
-            acc[jx][blk] = da_mfma(
-                a, da_frag(sm + S::oW1T, S::LDH, 16 * (blk * EC + c16), 32 * s, lane),
-                acc[jx][blk]);
-        }
-      }
-#pragma unroll
-      for (int jx = 0; jx < JX; ++jx) {
-        const int c16 = cg + DA_CG * jx;
-        if (c16 >= EC) continue;
-        const int e = 16 * c16 + (lane & 15);
-        const float qe = sq[e], due = sdu[e];
-        float dqp = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int r = 16 * rt + 4 * (lane >> 4) + i;
-          const float dfq = acc[jx][0][i], dfk = acc[jx][1][i];
-          const float dfd = acc[jx][2][i], dfm = acc[jx][3][i];
-          const float ke = bf16_to_f32(sm[S::oXT + (E + e) * DA_LDT + r]);
-          const float ar = __shfl(aj, r);
-          const float dk = fmaf(ar, due, dfk - dfd + dfm * qe);
-          if (r < p.L)
-            p.drows[(p.batch + b * p.L + r) * p.ld_drows + e] = f32_to_bf16_rne(dk);
-          dqp += dfq + dfd + dfm * ke;
-        }
-        dqp = swap32_sum(swap16_sum(dqp));  // the 4 row groups of column e
-        if (lane < 16) sdq[rt * E + e] = dqp;
-      }
-#pragma unroll
-      for (int i = 0; i < NW1; ++i) {
-        const int t = w + NWV * i;
-        if (t < H1T * NTX) {
-          const int m = t / NTX, n = t - m * NTX;
-#pragma unroll
-          for (int s = 0; s < 2; ++s)
-            if (s < kk)
-            gw1[i] = da_mfma(da_frag(sm + S::oZ1T, DA_LDT, 16 * m, 32 * s, lane),
-                             da_frag(sm + S::oXT, DA_LDT, 16 * n, 32 * s, lane), gw1[i]);
-        }
-      }
-    }
-    __syncthreads();
-    DA_STAMP(2 + 8 * sidx + 4);
-    if (tid < E) {
-      const float v = bf16_to_f32(p.dtop[b * p.lddt + tid]) + sdq[tid] + sdq[E + tid] +
-                      sdq[2 * E + tid] + sdq[3 * E + tid];
-      p.drows[b * p.ld_drows + tid] = f32_to_bf16_rne(v);
-    }
-    cur = nxt;
-    DA_STAMP(2 + 8 * sidx + 5);
-    ++sidx;
-  }
-
-  // ---- weight-gradient partials of this workgroup ----
-  float *part = p.part + static_cast<int64_t>(blockIdx.x) * p.P;
-  const int E4 = S::E4, H1 = p.H1, H2 = p.H2;
-  float *pw2 = part + H1 * E4, *pb1 = pw2 + H2 * H1, *pb2 = pb1 + H1, *pw3 = pb2 + H2,
-        *pb3 = pw3 + H2;
-#pragma unroll
-  for (int i = 0; i < NW1; ++i) {
-    const int t = w + NWV * i;
-    if (t < H1T * NTX) {
-      const int m = t / NTX, n = t - m * NTX;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int h = 16 * m + 4 * (lane >> 4) + j;
-        if (h < H1) part[h * E4 + 16 * n + (lane & 15)] = gw1[i][j];
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < NW2; ++i) {
-    const int t = w + NWV * i;
-    if (t < H2T * H1T) {
-      const int m = t / H1T, n = t - m * H1T;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int h2 = 16 * m + 4 * (lane >> 4) + j, h1 = 16 * n + (lane & 15);
-        if (h2 < H2 && h1 < H1) pw2[h2 * H1 + h1] = gw2[i][j];
-      }
-    }
-  }
-  // column partials: lanes l, l + 16, l + 32, l + 48 hold the same column; then the
-  // 4 row tiles (each column belongs to one column group)
-  __syncthreads();
-  float *red = reinterpret_cast<float *>(da_lds);  // [4][H1N + 2 H2N] (LDS now dead)
-  constexpr int RW = S::H1N + 2 * S::H2N;
-#pragma unroll
-  for (int jn = 0; jn < J1; ++jn) {
-    const int n = cg + DA_CG * jn;
-    const float v = swap32_sum(swap16_sum(gb1[jn]));
-    if (n < H1T && lane < 16) red[rt * RW + 16 * n + lane] = v;
-  }
-#pragma unroll
-  for (int jn = 0; jn < J2; ++jn) {
-    const int n = cg + DA_CG * jn;
-    const float v = swap32_sum(swap16_sum(gb2[jn])), u = swap32_sum(swap16_sum(gw3[jn]));
-    if (n < H2T && lane < 16) {
-      red[rt * RW + S::H1N + 16 * n + lane] = v;
-      red[rt * RW + S::H1N + S::H2N + 16 * n + lane] = u;
-    }
-  }
-  __syncthreads();
-  for (int c = tid; c < RW; c += DA_THREADS) {
-    const float v = red[c] + red[RW + c] + red[2 * RW + c] + red[3 * RW + c];
-    if (c < S::H1N) {
-      if (c < H1) pb1[c] = v;
-    } else if (c < S::H1N + S::H2N) {
-      if (c - S::H1N < H2) pb2[c - S::H1N] = v;
-    } else if (c - S::H1N - S::H2N < H2) {
-      pw3[c - S::H1N - S::H2N] = v;
-    }
-  }
-  if (tid == 0) pb3[0] = gb3;
-}
-
-// ---------------------------------------------------------------------------
 // backward, two samples in flight per workgroup (the default): waves 0-3 take one
 // sample, waves 4-7 the next, each wave one 16-row tile of its sample with ALL
 // column tiles.  No transposed copies: the operands whose k runs along history
@@ -1109,7 +766,7 @@ __global__ __launch_bounds__(DA_THREADS) void din_att_bwd2_kernel(DinAttArgs p, 
   DA_STAMP(0);
   da_zero_lds(da_lds, S::bf_end * 2);
   __syncthreads();
-  da_stage_weights<S, false>(p, sm, sb1, sb2, sw3);
+  da_stage_weights<S>(p, sm, sb1, sb2, sw3);
   const DaTask<E> task(tid & 255);  // X chunk tasks of this thread's slot
   int sidx = 0;
   DA_STAMP(1);
@@ -1531,9 +1188,6 @@ void da_set_attrs() {
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(din_att_fwd_kernel<E, H1T, H1K, H2T, H2K>),
                             hipFuncAttributeMaxDynamicSharedMemorySize,
                             static_cast<int>(S::fwd_bytes));
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(din_att_bwd_kernel<E, H1T, H1K, H2T, H2K>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(S::bwd_bytes));
   for (const void *k : {reinterpret_cast<const void *>(din_att_bwd2_kernel<E, H1T, H1K, H2T, H2K, false>),
                         reinterpret_cast<const void *>(din_att_bwd2_kernel<E, H1T, H1K, H2T, H2K, true>)})
     (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1552,15 +1206,6 @@ bool da_fwd_wg() {
   return e && e[0] == '1';
 }
 
-// MREC_DIN_BWD_ONE=1: the one-sample-per-workgroup backward (A/B and parity yardstick)
-bool da_one_sample() {
-  static const bool v = [] {
-    const char *e = std::getenv("MREC_DIN_BWD_ONE");
-    return e && e[0] == '1';
-  }();
-  return v;
-}
-
 bool da_supported(int E, int H1, int H2) {
   if (H1 % 4 != 0) return false;
 #define X(e, a, b, c, d) if (da_match<e, a, b, c, d>(E, H1, H2)) return true;
@@ -1572,17 +1217,16 @@ bool da_supported(int E, int H1, int H2) {
 }  // namespace
 
 static unsigned long long *g_da_stamps = nullptr;
-
-// MREC_DA_STAMP_FWD=1: the debug stamps go to the wave forward, not the backward
-static bool da_stamp_fwd() {
-  const char *e = std::getenv("MREC_DA_STAMP_FWD");
-  return e && e[0] == '1';
-}
+static bool g_da_stamps_fwd = false;  // the stamps go to the wave forward, not the backward
 
 extern "C" {
 
-// diagnostics (not in mrec.h): phase clocks of the next backward launches (NULL: off)
-void mrec_din_att_debug_stamps(void *buf) { g_da_stamps = static_cast<unsigned long long *>(buf); }
+// diagnostics (not in mrec.h): phase clocks of the next backward launches, or of the
+// next wave-forward launches with `forward` (NULL: off)
+void mrec_din_att_debug_stamps(void *buf, int forward) {
+  g_da_stamps = static_cast<unsigned long long *>(buf);
+  g_da_stamps_fwd = forward != 0;
+}
 
 int32_t mrec_din_att_supported(int32_t E, int32_t H1, int32_t H2) {
   return da_supported(E, H1, H2) ? 1 : 0;
@@ -1636,7 +1280,7 @@ mrec_status mrec_din_att_fwd(const void *rows, int64_t ld_rows, const int32_t *h
   p.a = a;
   p.top = static_cast<uint16_t *>(top);
   p.ldt = ldt;
-  p.stamps = da_stamp_fwd() ? g_da_stamps : nullptr;
+  p.stamps = g_da_stamps_fwd ? g_da_stamps : nullptr;
   const bool wg = da_fwd_wg();
   // one workgroup (8 sample waves) per CU, or one sample per workgroup
   const int64_t grid = wg ? std::min<int64_t>(batch, 2 * static_cast<int64_t>(da_cus()))
@@ -1694,17 +1338,13 @@ mrec_status mrec_din_att_bwd(const void *rows, int64_t ld_rows, int64_t batch, i
   p.ld_drows = ld_drows;
   p.part = part;
   p.P = mrec_din_att_param_count(E, H1, H2);
-  p.stamps = da_stamp_fwd() ? nullptr : g_da_stamps;
+  p.stamps = g_da_stamps_fwd ? nullptr : g_da_stamps;
   hipStream_t s = static_cast<hipStream_t>(stream);
 #define X(e, h1t, h1k, h2t, h2k)                                                              \
   if (da_match<e, h1t, h1k, h2t, h2k>(E, H1, H2)) {                                         \
     static const int once = (da_set_attrs<e, h1t, h1k, h2t, h2k>(), 1);                     \
     (void)once;                                                                             \
-    if (da_one_sample())                                                                    \
-      din_att_bwd_kernel<e, h1t, h1k, h2t, h2k>                                             \
-          <<<dim3(static_cast<unsigned>(parts)), DA_THREADS,                                \
-             DaShape<e, h1t, h1k, h2t, h2k>::bwd_bytes, s>>>(p);                            \
-    else if (const KClock kc = kclock_take(); kc.buf)                                       \
+    if (const KClock kc = kclock_take(); kc.buf)                                            \
       din_att_bwd2_kernel<e, h1t, h1k, h2t, h2k, true>                                      \
           <<<dim3(static_cast<unsigned>(parts)), DA_THREADS,                                \
              DaShape2<e, h1t, h1k, h2t, h2k>::bytes, s>>>(p, kc);                           \

@@ -23,10 +23,6 @@
 
 namespace mrec {
 
-#ifndef MREC_APPLY_EXP
-#define MREC_APPLY_EXP 0  // microbenchmark variants (tools/bench_apply.py, tools/gpu_apply_exp.sh); 0 = product
-#endif
-
 constexpr int kMaxPlanKeys = 8192;
 
 // ---------------------------------------------------------------------------
@@ -306,11 +302,7 @@ struct HotSeg {
       }
       __syncthreads();
       const int c1 = min(sn, c0 + kHotChunk);
-#if MREC_APPLY_EXP == 17  // (diagnostic: no hot-segment gradient loads)
-      if (live && sn < 0) {
-#else
       if (live) {
-#endif
 #pragma unroll 1
         for (int i0 = c0 + worker; i0 < c1; i0 += WPB * KB) {
           int bs[KB];
@@ -423,9 +415,6 @@ __device__ __forceinline__ void apply_segment(const BankArgs &bank, const ApplyA
 #pragma unroll
     for (int i = 0; i < PER; ++i) p[i] = l + i * LPR < n ? t.perm[d.z + l + i * LPR] : INT_MAX;
     int last = -1;
-#if MREC_APPLY_EXP == 16  // (diagnostic: no segment gradient loop)
-    if (n < 0)
-#endif
 #pragma unroll 1
     for (int k0 = 0; k0 < n; k0 += kSegBatch) {
       int sb[kSegBatch];
@@ -469,18 +458,9 @@ __global__ __launch_bounds__(256, MREC_APPLY_WAVES) void apply_hash_kernel(BankA
 #endif
   // the co-launched reductions take the leading workgroups: independent of the
   // embedding update, they start first instead of trailing it
-#if MREC_APPLY_EXP == 13  // (diagnostic: reductions trailing the apply blocks)
-  const int co_blocks = 0;
-  if (static_cast<int>(blockIdx.x) >= seg_blocks * (1 + kHotPer) + sm_blocks) {
-    co_reduce(co, blockIdx.x - seg_blocks * (1 + kHotPer) - sm_blocks);
-    return;
-  }
-#else
   const int co_blocks0 = co.start[co.n];
   if (static_cast<int>(blockIdx.x) < co_blocks0) {  // uniform
-#if MREC_APPLY_EXP != 12
     co_reduce(co, blockIdx.x);
-#endif
     return;
   }
   // the data-parallel dense SGD tiles (independent of the embedding update)
@@ -489,7 +469,6 @@ __global__ __launch_bounds__(256, MREC_APPLY_WAVES) void apply_hash_kernel(BankA
     return;
   }
   const int co_blocks = co_blocks0 + a.sgd_blocks;
-#endif
   if (a.d_step) a.seed += *a.d_step * 0x9e3779b97f4a7c15ull;
   constexpr int EPL = Vec<T>::EPL;
   constexpr int WPB = 256 / LPR;
@@ -505,9 +484,6 @@ __global__ __launch_bounds__(256, MREC_APPLY_WAVES) void apply_hash_kernel(BankA
   const int64_t *__restrict__ toff = table_offsets(ws, F, B);
 
   if (blk < seg_blocks) {  // uniform: the repeated rows of one (table, bucket)
-#if MREC_APPLY_EXP == 8 || MREC_APPLY_EXP == 14
-    return;
-#endif
     const int f = blk / kPlanBuckets, r = blk - f * kPlanBuckets;
     const BucketWs t = bucket_ws(ws, f, r, B);
     // the first pass's descriptor is loaded beside the header (unconditionally, from
@@ -530,9 +506,6 @@ __global__ __launch_bounds__(256, MREC_APPLY_WAVES) void apply_hash_kernel(BankA
     return;
   }
   if (blk < seg_blocks * (1 + kHotPer)) {  // uniform: hot segments k = h, h + kHotPer, ...
-#if MREC_APPLY_EXP == 10 || MREC_APPLY_EXP == 14
-    return;
-#endif
     const int q = blk - seg_blocks;
     const int fr = q / kHotPer, h = q - fr * kHotPer;
     const int f = fr / kPlanBuckets, r = fr - f * kPlanBuckets;
@@ -561,9 +534,6 @@ __global__ __launch_bounds__(256, MREC_APPLY_WAVES) void apply_hash_kernel(BankA
   }
 
   // a row hit once: one lookup, one update
-#if MREC_APPLY_EXP == 15
-  return;
-#endif
   const int64_t q = static_cast<int64_t>(blk - seg_blocks * (1 + kHotPer)) * WPB + worker;
   if (q >= B * F) return;  // whole workers
   const bool rowwise = MODE < 0 && a.mode == MREC_BWD_ROWWISE_ADAGRAD;
@@ -622,10 +592,6 @@ __global__ __launch_bounds__(256, MREC_APPLY_WAVES) void apply_hash_kernel(BankA
   } else if (live) {
     add_lookup_grad_v<EPL>(a, b, f, D, e0, v_lane, w_lane, v, acc);
   }
-#if MREC_APPLY_EXP == 9
-  if (acc[0] == 12345.f) *(float *)a.grad = acc[1];
-  return;
-#endif
   row_update<T, LPR, MODE>(bank, a, grow, e0, v_lane, w_lane, live, acc, raw);
 }
 

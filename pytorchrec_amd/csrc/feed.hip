@@ -10,7 +10,6 @@
 #include <algorithm>
 
 #include "common.h"
-#include <cstdlib>
 
 #include "feed_common.h"
 
@@ -22,7 +21,7 @@ __global__ __launch_bounds__(256) void batch_stage_kernel(const feed_u32x4 *__re
   constexpr int U = 4;  // independent 16-B loads per lane per trip
   const int64_t stride = static_cast<int64_t>(gridDim.x) * 256;
   int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-  for (; i < n16; i += U * stride) {  // (as feed_copy_body_u: U loads on every trip)
+  for (; i < n16; i += U * stride) {  // (as feed_copy_body: U loads on every trip)
     feed_u32x4 v[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -84,15 +83,8 @@ mrec_status build_feed_copy(const mrec_feed_job *job, int threads, FeedCopy *out
   out->dst = static_cast<uint4 *>(j.dst);
   out->state = reinterpret_cast<unsigned long long *>(j.d_state);
   const int64_t n16 = j.record_bytes / 16;
-  // 32 loads in flight per lane (MREC_FEED_UNROLL=4|16|32): fewer copying workgroups
-  static const int unroll = [] {
-    const char *e = std::getenv("MREC_FEED_UNROLL");
-    const int u = e ? std::atoi(e) : 32;
-    return u == 4 || u == 16 ? u : 32;
-  }();
-  out->unroll = unroll;
   out->blocks = static_cast<int>(std::max<int64_t>(
-      std::min<int64_t>((n16 + unroll * threads - 1) / (unroll * threads), 1024), 1));
+      std::min<int64_t>((n16 + kFeedUnroll * threads - 1) / (kFeedUnroll * threads), 1024), 1));
   return MREC_OK;
 }
 

@@ -18,8 +18,6 @@ struct FeedCopy {
   uint4 *dst;                 // the device slot
   unsigned long long *state;  // [0] cursor, [1] ticket
   int blocks;                 // workgroups of the launch that copy (0: none)
-  int unroll;                 // 16-B loads in flight per lane: 4, 16 or 32 (fewer copying
-                              // workgroups, so fewer CUs with host loads in flight)
   int64_t w16;                // the record's first w16 16-B pieces are uint16 -> int32 (ABI 29)
 };
 
@@ -32,9 +30,13 @@ __device__ __forceinline__ void feed_widen(feed_u32x4 *dst, int64_t p, feed_u32x
   dst[2 * p + 1] = feed_u32x4{v.z & 0xffffu, v.z >> 16, v.w & 0xffffu, v.w >> 16};
 }
 
+constexpr int kFeedUnroll = 32;  // 16-B loads in flight per lane: fewer copying workgroups,
+                                 // so fewer CUs with host loads in flight
+
 // run by workgroup `b` of the `fc.blocks` copying ones (THREADS threads each)
-template <int THREADS, int U = 4>
-__device__ __forceinline__ void feed_copy_body_u(const FeedCopy &fc, int b, long long *s_rec) {
+template <int THREADS>
+__device__ __forceinline__ void feed_copy_body(const FeedCopy &fc, int b, long long *s_rec) {
+  constexpr int U = kFeedUnroll;
   if (threadIdx.x == 0)
     *s_rec = static_cast<long long>(
         __hip_atomic_load(fc.state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -81,16 +83,6 @@ __device__ __forceinline__ void feed_copy_body_u(const FeedCopy &fc, int b, long
                          __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-}
-
-template <int THREADS>
-__device__ __forceinline__ void feed_copy_body(const FeedCopy &fc, int b, long long *s_rec) {
-  if (fc.unroll == 32)  // uniform
-    feed_copy_body_u<THREADS, 32>(fc, b, s_rec);
-  else if (fc.unroll == 16)
-    feed_copy_body_u<THREADS, 16>(fc, b, s_rec);
-  else
-    feed_copy_body_u<THREADS, 4>(fc, b, s_rec);
 }
 
 // host (feed.hip): validate a mrec_feed_job and fill *out (blocks: the copying

@@ -168,12 +168,8 @@ __device__ __forceinline__ void splitk_reduce_body(const GemmArgs &g, int64_t bi
   const int64_t slab = g.M * g.ldws;
   // fused SGD into tower images: 4 x 4 blocks over rows [0, M4), columns < N in
   // whole fours, the same fixed summation order per element
-#ifdef MREC_NO_BLK4  // diagnostics: the per-element path only
-  const bool blk4 = false;
-#else
   const bool blk4 = g.update && g.img_kind == kImgTower && (g.ldc % 4) == 0 &&
                     (reinterpret_cast<uintptr_t>(g.C) & 15) == 0;
-#endif
   const int64_t M4 = blk4 ? g.M / 4 * 4 : 0;
   const int64_t N4 = blk4 ? g.N / 4 : 0;  // whole column fours inside W
   if (blk4) {

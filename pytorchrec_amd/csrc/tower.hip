@@ -24,7 +24,6 @@
 // Outputs (h_l, dh_l, dx0) leave LDS as coalesced 16-B row stores behind each
 // layer, overlapped with the next layer's weight stream.
 #include <algorithm>
-#include <cstdlib>
 
 #include "common.h"
 #include "tower_common.h"
@@ -85,9 +84,7 @@ struct TowerArgs {
   int off_p;   // staged parameters (floats): biases, head_w, ws, b0, y, base, xs
   int p_bias[TW_MAXL], p_hw, p_ws, p_b0, p_y, p_base, p_xs, p_z, p_part;
   int lds_bytes;
-  int rotate;  // per-workgroup k-step rotation (MREC_TOWER_ROT=0 disables)
   unsigned long long *stamps;  // diagnostics: [grid][16] wall-clock stamps (NULL: off)
-  int store_mode;  // tower_store (MREC_TOWER_STORE)
   int kfrag;       // h_out / dh_out / x0_img are k-fragment images (tower_common.h)
   int nsteps;      // their k steps: ceil(B / 32)
   uint16_t *x0_img;
@@ -183,7 +180,7 @@ __device__ __forceinline__ void tower_mfma(f32x4 (&acc)[TW_TPW], __amdgpu_buffer
 template <int TW_PF>
 __device__ __forceinline__ void tower_layer_acc(f32x4 (&acc)[TW_TPW], const uint16_t *__restrict__ img,
                                                 int img_bytes, int ksteps, int ntiles, const char *in,
-                                                int s_in, int rotate) {
+                                                int s_in) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, r16 = lane & 15;
@@ -201,11 +198,7 @@ __device__ __forceinline__ void tower_layer_acc(f32x4 (&acc)[TW_TPW], const uint
   for (int i = 0; i < TW_TPW; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const char *brow = in + r16 * s_in + g * 16;
-  // rotate 1: blockIdx % ksteps; 2: (blockIdx / 8) % ksteps -- workgroups are dealt to the
-  // 8 XCDs round-robin, so this spreads the 32 workgroups of one XCD (one L2) over all
-  // k steps where mode 1 gives only ksteps / gcd(8, ksteps) distinct starts
-  const unsigned bq = rotate == 2 ? blockIdx.x >> 3 : blockIdx.x;
-  const int rot = rotate ? static_cast<int>(bq % static_cast<unsigned>(ksteps)) : 0;
+  const int rot = static_cast<int>(blockIdx.x % static_cast<unsigned>(ksteps));
   switch (nreal) {  // uniform per wave
     case 4: tower_mfma<4, TW_PF>(acc, rsrc, voff, img_bytes, brow, ksteps, rot); break;
     case 3: tower_mfma<3, TW_PF>(acc, rsrc, voff, img_bytes, brow, ksteps, rot); break;
@@ -219,14 +212,14 @@ template <bool BWD, int TW_PF>
 __device__ __forceinline__ void tower_layer(const uint16_t *__restrict__ img, int img_bytes,
                                             int ksteps, int width_out, const char *in, int s_in, char *out,
                                             int s_out, const float *__restrict__ bias,
-                                            const char *mask, int s_mask, int rotate) {
+                                            const char *mask, int s_mask) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, r16 = lane & 15;
   const int ntiles = tw_ceil(width_out, 16);
   const int ztiles = 2 * tw_ceil(width_out, 32);
   f32x4 acc[TW_TPW];
-  tower_layer_acc<TW_PF>(acc, img, img_bytes, ksteps, ntiles, in, s_in, rotate);
+  tower_layer_acc<TW_PF>(acc, img, img_bytes, ksteps, ntiles, in, s_in);
 
   // epilogue: lane holds rows c = 16 t + 4 g + r (r = 0..3) of column m = r16
 #pragma unroll
@@ -278,13 +271,13 @@ __device__ __forceinline__ uint2 pack_bf16x4(const float (&f)[4]) {
 template <int TW_PF>
 __device__ __forceinline__ void tower_cross_fwd(const uint16_t *__restrict__ img, int img_bytes, int d,
                                                 const char *x0b, const char *in, int s_x, char *out,
-                                                const float *bias, int rotate, uint2 (&zq)[TW_TPW]) {
+                                                const float *bias, uint2 (&zq)[TW_TPW]) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, r16 = lane & 15;
   const int ntiles = tw_ceil(d, 16), ztiles = 2 * tw_ceil(d, 32);
   f32x4 acc[TW_TPW];
-  tower_layer_acc<TW_PF>(acc, img, img_bytes, tw_ceil(d, 32), ntiles, in, s_x, rotate);
+  tower_layer_acc<TW_PF>(acc, img, img_bytes, tw_ceil(d, 32), ntiles, in, s_x);
 #pragma unroll
   for (int i = 0; i < TW_TPW; ++i) {
     const int t = wave + TW_WAVES * i;
@@ -315,14 +308,13 @@ __device__ __forceinline__ void tower_cross_fwd(const uint16_t *__restrict__ img
 template <int TW_PF>
 __device__ __forceinline__ void tower_cross_handoff(const uint16_t *__restrict__ img, int img_bytes,
                                                     int ksteps, int d, const char *gin, int s_g,
-                                                    const char *x0b, char *G, int s_x, char *dzo,
-                                                    int rotate) {
+                                                    const char *x0b, char *G, int s_x, char *dzo) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, r16 = lane & 15;
   const int ntiles = tw_ceil(d, 16), ztiles = 2 * tw_ceil(d, 32);
   f32x4 acc[TW_TPW];
-  tower_layer_acc<TW_PF>(acc, img, img_bytes, ksteps, ntiles, gin, s_g, rotate);
+  tower_layer_acc<TW_PF>(acc, img, img_bytes, ksteps, ntiles, gin, s_g);
 #pragma unroll
   for (int i = 0; i < TW_TPW; ++i) {
     const int t = wave + TW_WAVES * i;
@@ -351,14 +343,14 @@ __device__ __forceinline__ void tower_cross_handoff(const uint16_t *__restrict__
 template <int TW_PF>
 __device__ __forceinline__ void tower_cross_bwd(const uint16_t *__restrict__ img, int img_bytes, int d,
                                                 const char *x0b, char *G, int s_x, const char *dzi,
-                                                char *dzo, int s_g, int rotate, const uint2 (&zq)[TW_TPW],
+                                                char *dzo, int s_g, const uint2 (&zq)[TW_TPW],
                                                 f32x4 (&dacc)[TW_TPW], bool last) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, r16 = lane & 15;
   const int ntiles = tw_ceil(d, 16), ztiles = 2 * tw_ceil(d, 32);
   f32x4 acc[TW_TPW];
-  tower_layer_acc<TW_PF>(acc, img, img_bytes, tw_ceil(d, 32), ntiles, dzi, s_g, rotate);
+  tower_layer_acc<TW_PF>(acc, img, img_bytes, tw_ceil(d, 32), ntiles, dzi, s_g);
 #pragma unroll
   for (int i = 0; i < TW_TPW; ++i) {
     const int t = wave + TW_WAVES * i;
@@ -395,13 +387,13 @@ __device__ __forceinline__ void tower_cross_bwd(const uint16_t *__restrict__ img
 }
 
 // rows [0, 16) of an LDS block -> global bf16 [B, ld], columns [0, round8(width)).
-// store_mode 1 (default): sc1 write-through stores, which do not keep the line in
-// the XCD's L2 (MI355X_MICROARCH.md, store flavours), so the ~2.5 MB of
-// activation / gradient rows an XCD writes per launch do not evict the weight
-// images every workgroup re-reads; 0: plain stores; 2: no stores (timing only).
+// sc1 write-through stores, which do not keep the line in the XCD's L2
+// (MI355X_MICROARCH.md, store flavours), so the ~2.5 MB of activation / gradient
+// rows an XCD writes per launch do not evict the weight images every workgroup
+// re-reads.
 __device__ __forceinline__ void tower_store(const char *blk, int s_blk, int width, uint16_t *dst,
-                                            int64_t ld, int64_t row0, int64_t B, int store_mode) {
-  if (!dst || store_mode == 2) return;
+                                            int64_t ld, int64_t row0, int64_t B) {
+  if (!dst) return;
   const int chunks = tw_ceil(width, 8);
   const int rows = static_cast<int>(min<int64_t>(TW_ROWS, B - row0));
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -411,10 +403,7 @@ __device__ __forceinline__ void tower_store(const char *blk, int s_blk, int widt
     if (r < rows) {
       const u32x4 v = *reinterpret_cast<const u32x4 *>(blk + r * s_blk + c * 16);
       const int off = static_cast<int>((r * ld + c * 8) * 2);
-      if (store_mode == 1)
-        __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, off, 0, 16);
-      else
-        __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, off, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, off, 0, 16);
     }
   }
 }
@@ -426,17 +415,14 @@ __device__ __forceinline__ void tower_store(const char *blk, int s_blk, int widt
 // no workgroup owns it, so the image never holds stale rows (the weight-gradient
 // kernel multiplies whole steps).
 __device__ __forceinline__ void tower_store_kfrag(const char *blk, int s_blk, int width, uint16_t *img,
-                                                  int nsteps, int64_t row0, int64_t B, int store_mode) {
-  if (!img || store_mode == 2) return;
+                                                  int nsteps, int64_t row0, int64_t B) {
+  if (!img) return;
   const int ctiles = tw_ceil(width, 16);
   const int st = static_cast<int>(row0 >> 5), h = static_cast<int>((row0 >> 4) & 1);
   const int bytes = static_cast<int>(kfrag_elems(B, width) * 2);
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(img, 0, bytes, 0x00020000);
-  auto put = [&](u32x4 v, int off) {  // store_mode 1: write-through (see tower_store)
-    if (store_mode == 1)
-      __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, off, 0, 16);
-    else
-      __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, off, 0, 0);
+  auto put = [&](u32x4 v, int off) {  // write-through (see tower_store)
+    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, off, 0, 16);
   };
   // 16 lanes per (tile t, 8-row group gl): two ds_read_b64_tr_b16 give lane i the 8
   // rows of column 16 t + i (lane i addresses row 8 gl + i / 4 (+ 4), columns
@@ -481,9 +467,9 @@ __device__ __forceinline__ void tower_store_kfrag(const char *blk, int s_blk, in
 __device__ __forceinline__ void tower_out(const TowerArgs &a, const char *blk, int s_blk, int width,
                                           uint16_t *dst, int64_t ld, int64_t row0) {
   if (a.kfrag)
-    tower_store_kfrag(blk, s_blk, width, dst, a.nsteps, row0, a.B, a.store_mode);
+    tower_store_kfrag(blk, s_blk, width, dst, a.nsteps, row0, a.B);
   else
-    tower_store(blk, s_blk, width, dst, ld, row0, a.B, a.store_mode);
+    tower_store(blk, s_blk, width, dst, ld, row0, a.B);
 }
 
 // diagnostics: stamps go to LDS (a global store before a barrier would be waited
@@ -593,7 +579,7 @@ __global__ __launch_bounds__(TW_THREADS) void tower_kernel(TowerArgs a, KClock k
       char *out = lds + a.off_xc[c & 1];
       uint2 zq[TW_TPW];
       tower_cross_fwd<TW_PF>(a.cwf[c], a.cw_bytes, d, lds + a.off_x, in, a.s_x, out,
-                             prm + a.p_cbias[c], a.rotate, zq);
+                             prm + a.p_cbias[c], zq);
 #pragma unroll
       for (int i = 0; i < TW_TPW; ++i) {
 #pragma unroll
@@ -603,8 +589,8 @@ __global__ __launch_bounds__(TW_THREADS) void tower_kernel(TowerArgs a, KClock k
       __syncthreads();
       if (a.kfrag) {  // the cross weight gradients' X operands: x_0 = x0, x_{c+1}
         if (c == 0)
-          tower_store_kfrag(lds + a.off_x, a.s_x, d, a.x0_img, a.nsteps, row0, a.B, a.store_mode);
-        tower_store_kfrag(out, a.s_x, d, a.cx_img[c], a.nsteps, row0, a.B, a.store_mode);
+          tower_store_kfrag(lds + a.off_x, a.s_x, d, a.x0_img, a.nsteps, row0, a.B);
+        tower_store_kfrag(out, a.s_x, d, a.cx_img[c], a.nsteps, row0, a.B);
       }
     }
     off_in0 = a.off_xc[(a.C - 1) & 1];
@@ -616,14 +602,13 @@ __global__ __launch_bounds__(TW_THREADS) void tower_kernel(TowerArgs a, KClock k
     const char *in = lds + (l == 0 ? off_in0 : a.off_h[l - 1]);
     const int s_in = l == 0 ? a.s_x : a.s_h[l - 1];
     tower_layer<false, TW_PF>(a.wf[l], a.wf_bytes[l], tw_ceil(a.width[l], 32), a.width[l + 1], in, s_in,
-                       lds + a.off_h[l], a.s_h[l], prm + a.p_bias[l], nullptr, 0, a.rotate);
+                       lds + a.off_h[l], a.s_h[l], prm + a.p_bias[l], nullptr, 0);
     __syncthreads();
     TW_STAMP(2 + l);
     // x0's k-fragment image leaves behind layer 1 (x0's block stays in LDS): issued
     // before it, its stores delayed the first weight fragments by ~1 us
     if (!CROSS && l == 0 && a.kfrag)
-      tower_store_kfrag(lds + a.off_x, a.s_x, a.width[0], a.x0_img, a.nsteps, row0, a.B,
-                        a.store_mode);
+      tower_store_kfrag(lds + a.off_x, a.s_x, a.width[0], a.x0_img, a.nsteps, row0, a.B);
     if (l + 1 < L) tower_out(a, lds + a.off_h[l], a.s_h[l], a.width[l + 1], a.h_out[l], a.ld_h[l], row0);
   }
 
@@ -745,10 +730,10 @@ __global__ __launch_bounds__(TW_THREADS) void tower_kernel(TowerArgs a, KClock k
     const int s_mask = l > 0 ? a.s_h[l - 1] : 0;
     if (CROSS && l == 0)  // dx_C -> G (off_xc[0], free in the backward), dz_{C-1} -> gout
       tower_cross_handoff<TW_PF>(a.wb[0], a.wb_bytes[0], tw_ceil(a.width[1], 32), a.width[0], gin,
-                                 a.s_g, lds + a.off_x, lds + a.off_xc[0], a.s_x, gout, a.rotate);
+                                 a.s_g, lds + a.off_x, lds + a.off_xc[0], a.s_x, gout);
     else
       tower_layer<true, TW_PF>(a.wb[l], a.wb_bytes[l], tw_ceil(a.width[l + 1], 32), a.width[l], gin,
-                               a.s_g, gout, a.s_g, nullptr, mask, s_mask, a.rotate);
+                               a.s_g, gout, a.s_g, nullptr, mask, s_mask);
     __syncthreads();
     TW_STAMP(7 + (L - 1 - l));
     if (l > 0) {
@@ -765,8 +750,7 @@ __global__ __launch_bounds__(TW_THREADS) void tower_kernel(TowerArgs a, KClock k
         s_last = old == gridDim.x - 1 ? 1u : 0u;
       }
       if (a.kfrag)
-        tower_store_kfrag(gout, a.s_g, a.width[0], a.cdz_img[a.C - 1], a.nsteps, row0, a.B,
-                          a.store_mode);
+        tower_store_kfrag(gout, a.s_g, a.width[0], a.cdz_img[a.C - 1], a.nsteps, row0, a.B);
     } else {
       // the loss: this workgroup's partial as a write-through granule + a relaxed
       // agent ticket (cdna_hip_programming.md §6 G16), before the dx0 stores so the
@@ -781,7 +765,7 @@ __global__ __launch_bounds__(TW_THREADS) void tower_kernel(TowerArgs a, KClock k
                                                     __HIP_MEMORY_SCOPE_AGENT);
         s_last = old == gridDim.x - 1 ? 1u : 0u;
       }
-      tower_store(gout, a.s_g, a.width[0], a.dx0, a.ld_dx0, row0, a.B, a.store_mode);
+      tower_store(gout, a.s_g, a.width[0], a.dx0, a.ld_dx0, row0, a.B);
     }
     cur ^= 1;
   }
@@ -803,13 +787,13 @@ __global__ __launch_bounds__(TW_THREADS) void tower_kernel(TowerArgs a, KClock k
       }
       char *dzo = lds + a.off_g[cur ^ 1];
       tower_cross_bwd<TW_PF>(a.cwb[c], a.cw_bytes, d, lds + a.off_x, G, a.s_x, lds + a.off_g[cur],
-                             dzo, a.s_g, a.rotate, zq, dacc, c == 0);
+                             dzo, a.s_g, zq, dacc, c == 0);
       __syncthreads();
       if (c > 0) {
         if (a.kfrag)
-          tower_store_kfrag(dzo, a.s_g, d, a.cdz_img[c - 1], a.nsteps, row0, a.B, a.store_mode);
+          tower_store_kfrag(dzo, a.s_g, d, a.cdz_img[c - 1], a.nsteps, row0, a.B);
       } else {
-        tower_store(G, a.s_x, d, a.dx0, a.ld_dx0, row0, a.B, a.store_mode);
+        tower_store(G, a.s_x, d, a.dx0, a.ld_dx0, row0, a.B);
       }
       cur ^= 1;
     }
@@ -988,17 +972,7 @@ mrec_status mrec_tower_fwd_bwd(const mrec_tower_args *p, mrec_stream stream) {
   a.ticket = s.ticket;
   a.loss = s.loss;
   a.invB = 1.f / static_cast<float>(s.batch);
-  static const int rot_env = [] {  // MREC_TOWER_ROT: 0 off, 1 blockIdx, 2 per-XCD index
-    const char *e = getenv("MREC_TOWER_ROT");
-    return e ? atoi(e) : 1;
-  }();
-  a.rotate = rot_env;
   a.stamps = g_tower_stamps;
-  static const int store_env = [] {
-    const char *e = getenv("MREC_TOWER_STORE");
-    return e ? atoi(e) : 1;
-  }();
-  a.store_mode = store_env;
   a.kfrag = kf ? 1 : 0;
   a.nsteps = static_cast<int>((s.batch + 31) / 32);
   a.x0_img = kf ? static_cast<uint16_t *>(s.x0_img) : nullptr;
@@ -1071,9 +1045,7 @@ mrec_status mrec_tower_fwd_bwd(const mrec_tower_args *p, mrec_stream stream) {
   constexpr int kMaxDyn = 160 * 1024 - 256;  // the kernel's static LDS (s_last) is on top
   MREC_CHECK_ARG(a.lds_bytes <= kMaxDyn, "activation blocks exceed the 160 KiB LDS");
   static int attr_set = [] {
-    for (const void *k : {reinterpret_cast<const void *>(tower_kernel<4, false, false>),
-                          reinterpret_cast<const void *>(tower_kernel<6, false, false>),
-                          reinterpret_cast<const void *>(tower_kernel<8, false, false>),
+    for (const void *k : {reinterpret_cast<const void *>(tower_kernel<TW_PF_DEFAULT, false, false>),
                           reinterpret_cast<const void *>(tower_kernel<TW_PF_DEFAULT, true, false>),
                           reinterpret_cast<const void *>(tower_kernel<TW_PF_DEFAULT, false, true>),
                           reinterpret_cast<const void *>(tower_kernel<TW_PF_DEFAULT, true, true>)})
@@ -1082,28 +1054,19 @@ mrec_status mrec_tower_fwd_bwd(const mrec_tower_args *p, mrec_stream stream) {
     return 1;
   }();
   (void)attr_set;
-  static const int pf_env = [] {  // MREC_TOWER_PF: weight k steps in flight per wave
-    const char *e = getenv("MREC_TOWER_PF");
-    const int v = e ? atoi(e) : TW_PF_DEFAULT;
-    return (v == 4 || v == 6) ? v : 8;
-  }();
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t grid = (s.batch + TW_ROWS - 1) / TW_ROWS;
   const dim3 gd(static_cast<unsigned>(grid));
   const KClock kc = kclock_take();
-  if (C > 0) {  // the cross network runs at the default prefetch depth
+  if (C > 0) {
     if (kc.buf)
       tower_kernel<TW_PF_DEFAULT, true, true><<<gd, TW_THREADS, a.lds_bytes, st>>>(a, kc);
     else
       tower_kernel<TW_PF_DEFAULT, false, true><<<gd, TW_THREADS, a.lds_bytes, st>>>(a, kc);
-  } else if (kc.buf) {  // (the clocked instantiation is the default prefetch depth's)
+  } else if (kc.buf) {
     tower_kernel<TW_PF_DEFAULT, true, false><<<gd, TW_THREADS, a.lds_bytes, st>>>(a, kc);
-  } else if (pf_env == 8) {
-    tower_kernel<8, false, false><<<gd, TW_THREADS, a.lds_bytes, st>>>(a, kc);
-  } else if (pf_env == 6) {
-    tower_kernel<6, false, false><<<gd, TW_THREADS, a.lds_bytes, st>>>(a, kc);
   } else {
-    tower_kernel<4, false, false><<<gd, TW_THREADS, a.lds_bytes, st>>>(a, kc);
+    tower_kernel<TW_PF_DEFAULT, false, false><<<gd, TW_THREADS, a.lds_bytes, st>>>(a, kc);
   }
   return launch_status("mrec_tower_fwd_bwd");
 }

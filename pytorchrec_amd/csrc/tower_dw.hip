@@ -32,9 +32,6 @@
 
 namespace mrec {
 
-#ifndef MREC_TDW_EXP
-#define MREC_TDW_EXP 0
-#endif
 #ifndef MREC_DW_PF
 #define MREC_DW_PF 4
 #endif
@@ -145,30 +142,19 @@ __global__ __launch_bounds__(64) void tower_dw_kernel(DwArgs a, KClock kc) {
     load(p, p);
     __builtin_amdgcn_sched_barrier(0);  // issue order = consumption order (waitcnt)
   }
-#if MREC_TDW_EXP == 4  // diagnostics: no main loop
-  const int total = 0;
-#else
   const int total = (s_n + PF - 1) / PF * PF;
-#endif
   for (int base = 0; base < total; base += PF) {
 #pragma unroll
     for (int p = 0; p < PF; ++p) {
       bf16x8 bj[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) bj[j] = ones_j[j] ? ones : fb[p][j];
-#if MREC_TDW_EXP == 1  // diagnostics: loads only
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[i][0][0] += __builtin_bit_cast(float, int(fa[p][i][0] ^ bj[i][1]));
-#else
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[p][i], bj[j], acc[i][j], 0, 0, 0);
-#endif
-#if MREC_TDW_EXP != 2  // 2: MFMAs on the prologue's fragments only
       load(p, base + p + PF);
-#endif
       __builtin_amdgcn_sched_barrier(0);
     }
   }
@@ -192,9 +178,6 @@ __global__ __launch_bounds__(64) void tower_dw_kernel(DwArgs a, KClock kc) {
     const int m = m0 + row;
     if (m < y.n_out && n < y.ldws) {
       const float4 v = *reinterpret_cast<const float4 *>(tile + row * 68 + (lane & 15) * 4);
-#if MREC_TDW_EXP == 3  // diagnostics: no slab stores (kept alive)
-      if (v.x == 1.2345e-30f)
-#endif
       *reinterpret_cast<float4 *>(slab + static_cast<int64_t>(m) * y.ldws + n) = v;
     }
   }

@@ -20,7 +20,6 @@ row starts 16-byte aligned.
 from __future__ import annotations
 
 import ctypes
-import os
 from typing import Optional, Sequence
 
 import torch
@@ -66,9 +65,6 @@ def _split_beside(M: int, N: int, K: int, budget: int = 256) -> int:
         s += 1
     return s
 
-
-# K slices of a fused-SGD weight-gradient GEMM (0: _split_for's choice)
-_DW_SPLIT = int(os.environ.get("MREC_DW_SPLIT", "0"))
 
 _MASK_TAG = "_mrec_relu_masked"
 _RELU_OUT = "_mrec_relu_out"
@@ -474,7 +470,7 @@ class _LinearFn(torch.autograd.Function):
                             _mrec.GEMM_FULL, b_cols=K, mask=x if ctx.x_relu else None)
                 calls.append(cdx)
                 dx = cdx.out
-            sk = _DW_SPLIT or _split_beside(N, K + 1, M)
+            sk = _split_beside(N, K + 1, M)
             if dpg is not None:
                 cdw = _Call(dy, _mrec.LAYOUT_COL, x, _mrec.LAYOUT_COL, N, K, M,
                             _mrec.GEMM_PARTIAL if sk > 1 else _mrec.GEMM_FULL,
@@ -634,7 +630,7 @@ class _CrossNetFn(torch.autograd.Function):
                 # dW reduction); this layer's reduction rides in the next launch
                 cdx = _Call(dz, _mrec.LAYOUT_ROW, wt, _mrec.LAYOUT_ROW, M, xl.shape[1], d,
                             _mrec.GEMM_FULL, b_cols=d, add=add)
-                sk = _DW_SPLIT or _split_beside(d, d + 1, M)
+                sk = _split_beside(d, d + 1, M)
                 ph = _mrec.GEMM_PARTIAL if sk > 1 else _mrec.GEMM_FULL
                 if dpg is not None:
                     cdw = _Call(dz, _mrec.LAYOUT_COL, xl, _mrec.LAYOUT_COL, d, d, M, ph,
@@ -805,25 +801,19 @@ class _DinRowsFeatFn(torch.autograd.Function):
         return d_rows, None, None, None
 
 
-# opt-in (MREC_DIN_TOWER=1): measured at C4 the score tower is slower than the
-# GEMMs (fwd 279, bwd 527, weight gradients 213 us vs ~360 us for the GEMM path in
-# all): 12,800 16-row workgroups at 2 per CU run 25 residency rounds of the tower's
-# latency chain, and the k-fragment images of 204,800 rows go through HBM
-DIN_TOWER = os.environ.get("MREC_DIN_TOWER", "0") == "1"
-
-
 def _din_scores(feat: torch.Tensor, att_mlp, att_out: torch.nn.Linear) -> torch.Tensor:
-    """Attention-unit scores [B L, 1] fp32: the attention MLP's GEMMs + Linear(h, 1),
-    or the score tower (one launch each way) with MREC_DIN_TOWER=1."""
-    if DIN_TOWER and tower_supported(feat, att_mlp, att_out):
-        return score_tower(feat, att_mlp, att_out).reshape(-1, 1)
+    """Attention-unit scores [B L, 1] fp32: the attention MLP's GEMMs + Linear(h, 1).
+    Not the score tower (score_tower): measured at C4 it is slower than the GEMMs
+    (fwd 279, bwd 527, weight gradients 213 us vs ~360 us for the GEMM path in all):
+    12,800 16-row workgroups at 2 per CU run 25 residency rounds of the tower's
+    latency chain, and the k-fragment images of 204,800 rows go through HBM."""
     h = att_mlp(feat)
     return linear(h, att_out.weight, att_out.bias, out_dtype=torch.float32)
 
 
 # the fused attention unit (mrec_din_att_*, din_att.hip) is the default for the
-# compiled shapes; MREC_DIN_FUSED=0 selects the layered kernels (A/B, parity tests)
-DIN_FUSED = os.environ.get("MREC_DIN_FUSED", "1") == "1"
+# compiled shapes; False selects the layered kernels (the parity tests set it)
+DIN_FUSED = True
 
 
 def _din_att_linears(att_mlp, att_out):
@@ -1159,11 +1149,10 @@ def ctr_head_bce(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Ten
 # fused MLP tower + CTR head + BCE (mrec_tower_fwd_bwd)
 # ----------------------------------------------------------------------------
 
-TOWER = os.environ.get("MREC_TOWER", "1") == "1"
+TOWER = True  # False: the layered kernels (the parity tests set it)
 TOWER_MAXL, TOWER_MAXW = 4, 512
-# DCN-v2 cross layers inside the tower launch (MREC_TOWER_CROSS=0: the layered
-# cross network of _CrossNetFn ahead of the tower)
-TOWER_CROSS = os.environ.get("MREC_TOWER_CROSS", "1") == "1"
+# DCN-v2 cross layers inside the tower launch (more: the layered cross network of
+# _CrossNetFn ahead of the tower)
 TOWER_MAXC = 3
 
 
@@ -1178,7 +1167,7 @@ def tower_supported(x0: torch.Tensor, mlp, head: torch.nn.Linear, xs=None, cross
     ahead of it when the batch takes mrec_tower_dw."""
     if cross:
         lins = _mlp_linears(mlp) if (hasattr(mlp, "mlp") and mlp.mlp) else None
-        if not TOWER_CROSS or not lins or len(cross) > TOWER_MAXC:
+        if not lins or len(cross) > TOWER_MAXC:
             return False
         d = lins[0].in_features
         if any(c.in_features != d or c.out_features != d or c.weight.dtype != torch.float32
@@ -1226,13 +1215,11 @@ def _tdw_splits(B: int, widths=None) -> int:
     faster and double the slabs the reduction reads) and for DIN's top tower (16
     tiles: 16 slices 0.2256-0.2258 ms/step, 8: 0.2245-0.2252, 4: 0.2233-0.2240), 64
     for DIN's layered attention unit (8 tiles over 204,800 rows)."""
-    if os.environ.get("MREC_TOWER_DW", "1") == "0" or B < 256:
+    if B < 256:
         return 0
-    env = os.environ.get("MREC_TDW_SPLITS")  # A/B knob
-    # at least 4 (C3's 245 tiles: 2 slices 0.1243 ms/step, 4: 0.1194; 3 and 5 slower,
-    # tools/gpu_ab_splits.sh)
-    want = int(env) if env else (4 if widths is None else
-                                 max(4, min(64, 640 // _tdw_tiles(widths), max(4, B // 1024))))
+    # at least 4 (C3's 245 tiles: 2 slices 0.1243 ms/step, 4: 0.1194; 3 and 5 slower)
+    want = (4 if widths is None else
+            max(4, min(64, 640 // _tdw_tiles(widths), max(4, B // 1024))))
     for s in range(want, 1, -1):
         if B // s >= 256 and _eff_split(B, s) == s:
             return s

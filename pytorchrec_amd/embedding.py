@@ -35,7 +35,6 @@ Update modes (``EmbeddingBank.update``):
 from __future__ import annotations
 
 import ctypes
-import os
 from typing import List, Optional, Sequence
 
 import torch
@@ -376,10 +375,8 @@ def _chunks(batch: int):
 
 
 LARGE_MAX_ROWS = 1 << 24  # banks up to this many rows take the large-batch path
-# MREC_LARGE_BATCH=0: chunked plan/apply pairs instead (one SGD step per chunk)
-LARGE_BATCH = os.environ.get("MREC_LARGE_BATCH", "1") == "1"
-# MREC_LARGE_FUSED=0: the plan / apply pair instead of mrec_emb_bwd_large_fused
-LARGE_FUSED = os.environ.get("MREC_LARGE_FUSED", "1") == "1"
+# False: the plan / apply pair instead of mrec_emb_bwd_large_fused (the parity tests set it)
+LARGE_FUSED = True
 
 
 def _large_ws(bank: EmbeddingBank, batch: int) -> torch.Tensor:
@@ -441,13 +438,13 @@ def _backward_into_bank(bank: EmbeddingBank, ids, batch, plan_ws, dx=None, dfm=N
         ws, wsb = plan_ws.get() if isinstance(plan_ws, _AsyncPlan) else plan_ws
         _apply(bank, ws, wsb, batch, dx, dfm, fm_sum, x0, dw, grad)
         return grad
-    if batch > _mrec.BWD_MAX_BATCH and bank.total_rows <= LARGE_MAX_ROWS and LARGE_BATCH:
+    if batch > _mrec.BWD_MAX_BATCH and bank.total_rows <= LARGE_MAX_ROWS:
         _backward_large(bank, ids, batch, grad, dx, dfm, fm_sum, x0, dw)
         return grad
     if bank.update == "adam" and batch > _mrec.BWD_MAX_BATCH:
         raise NotImplementedError("fused Adam takes one apply per step: batches above "
                                   f"{_mrec.BWD_MAX_BATCH} lookups per table need the large-batch "
-                                  "path (MREC_LARGE_BATCH=1, banks up to 2^24 rows)")
+                                  "path (banks up to 2^24 rows)")
     for s, c in _chunks(batch):
         if c == 0:
             continue

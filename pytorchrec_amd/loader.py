@@ -37,7 +37,6 @@ from __future__ import annotations
 
 import ctypes
 import math
-import os
 from typing import Dict, Iterator, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
@@ -215,8 +214,7 @@ class ColumnarLoader:
         self.side_stream = copy == "side"
         self.epoch = 0
         # 16-bit ids in the host records when the copy is a kernel that widens them
-        narrow = (self.device.type == "cuda" and copy == "kernel"
-                  and os.environ.get("MREC_FEED_NARROW", "1") != "0")
+        narrow = self.device.type == "cuda" and copy == "kernel"
         self.layout = PackedLayout(dataset, self.batch_size, narrow=narrow)
         self._host: Optional[Tensor] = None
         self._packed: Optional[List[int]] = None  # batch sizes of a prepared epoch

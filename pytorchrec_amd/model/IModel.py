@@ -304,7 +304,7 @@ class IModel(Module, IWithArguments, ABC):
         self._dp_sgd_table = None
         from pytorchrec_amd.sharding import ShardedEmbeddingBank
         for b in self.embedding_banks():  # the owner apply runs the dense SGD (ABI 28)
-            if isinstance(b, ShardedEmbeddingBank) and os.environ.get("MREC_DP_INLINE_SGD", "1") == "1":
+            if isinstance(b, ShardedEmbeddingBank):
                 b.dp_inline_sgd = self._dp_inline_sgd
 
     def _dp_flat_step(self):

@@ -11,10 +11,11 @@ compact exchange, include/mrec.h ABI 19):
   owner   rows of the received ids -> one 36-B record per        mrec_shard_gather_wire
           distinct row, packed per owner over all tables
           all_to_all records back                                (equal split)
-  sender  records -> slot rows, the part prefixes of its own     mrec_shard_wire_unpack_ex
-          record layout
-          interaction on the slot rows, with the sender's        mrec_interact_fwd_ex
-          backward plan over pos in the same launch
+  sender  interaction straight on the received records (which    mrec_interact_fwd_rec
+          it also writes out as slot rows), with the sender's    (banks that are not
+          backward plan over pos in the same launch              bf16 / 64-B rows:
+                                                                 mrec_shard_wire_unpack_ex
+                                                                 + mrec_interact_fwd_ex)
   ---- backward ----
   sender  gradient sum of each slot's lookups (fixed ascending   mrec_emb_bwd_apply_rec
           order) written straight as one record per distinct     (ABI 26; batches past
@@ -53,7 +54,6 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import math
-import os
 from typing import List, Optional, Sequence
 
 import torch
@@ -261,8 +261,7 @@ class ShardedEmbeddingBank(EmbeddingBank):
         # smaller chunks (W = 16: 7,168 samples; W >= 127 is not supported)
         if W + 1 > 128:
             raise ValueError(f"row sharding supports world sizes up to 127, not {W}")
-        cb = int(os.environ.get("MREC_SHARD_CHUNK", type(self).chunk_batch))  # (A/B knob)
-        self.chunk_batch = min(cb, 1024 * (128 // (W + 1)))
+        self.chunk_batch = min(type(self).chunk_batch, 1024 * (128 // (W + 1)))
         # slots per (owner, table[, chunk]): distinct ids of one chunk on the compact
         # exchange, lookups of the whole batch on the slot exchange (which does not
         # chunk); the `compact` setter switches a defaulted cap
@@ -290,7 +289,7 @@ class ShardedEmbeddingBank(EmbeddingBank):
         # 28; a power of two <= 16) and its scratch.  1 by default: 2 or 4 quarters
         # measured no faster at C2's shape (11.9-12.2 us against 11.9 at W = 1; the
         # launch is a chain of id loads, barriers and stores, not of inserts)
-        self.dedup_quarters = int(os.environ.get("MREC_DEDUP_QUARTERS", "1"))
+        self.dedup_quarters = 1
         self._dedup_scratch = None
 
     def dedup_scratch(self, chunks: int) -> torch.Tensor:
@@ -388,7 +387,7 @@ class ShardedEmbeddingBank(EmbeddingBank):
         if ov & 4:
             raise RuntimeError("row-sharded dedup bucketize: a quarter workgroup's wait for "
                                "its siblings timed out (slots of that table are not valid); "
-                               "MREC_DEDUP_QUARTERS=1 runs one workgroup per table")
+                               "dedup_quarters = 1 runs one workgroup per table")
         if ov & 2:
             raise RuntimeError(f"row-sharded compact exchange overflow: more than cap_rows="
                                f"{self.cap_rows} distinct ids for one owner over all tables in a "
@@ -714,10 +713,8 @@ def owner_plan_job(bank: ShardedEmbeddingBank, recv_ids: torch.Tensor, part: int
 def records_direct(bank: ShardedEmbeddingBank) -> bool:
     """Whether the interaction reads the received records itself
     (mrec_interact_fwd_rec: bf16 64-B slot rows; a lazy-Adam bank's rows were caught
-    up by the owner's gather) instead of after an unpack launch; MREC_SHARD_UNPACK=1
-    forces the unpack (A/B)."""
-    return (bank.weight.dtype == torch.bfloat16 and bank.row_stride * 2 == 64
-            and os.environ.get("MREC_SHARD_UNPACK") != "1")
+    up by the owner's gather) instead of after an unpack launch (other banks)."""
+    return bank.weight.dtype == torch.bfloat16 and bank.row_stride * 2 == 64
 
 
 def shard_interact(bank: ShardedEmbeddingBank, rows_recv: torch.Tensor, pos: torch.Tensor,

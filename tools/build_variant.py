@@ -1,5 +1,5 @@
 """Build a diagnostic variant of libmrec with extra preprocessor flags:
-    python tools/build_variant.py NAME -DMREC_APPLY_EXP=15 [...]
+    python tools/build_variant.py NAME -DMREC_KC_CAT [...]
 -> pytorchrec_amd/lib/variants/NAME/libmrec.so (run with MREC_LIB_PATH=...).  The
 product library (pytorchrec_amd/build.py) is not touched."""
 import os
