@@ -95,10 +95,16 @@ constexpr int kPlanBuckets = 1 << MREC_PLAN_BUCKETS_LOG2;  // workgroups per tab
 constexpr int kShortSeg = MREC_SHORT_SEG;  // longer segments: the bucket's long list
 constexpr uint32_t kEmpty = 0xffffffffu;
 
-// segments up to this many lookups are summed by one wave of the apply (one
-// lookup per LPR-lane worker), longer ones by a whole workgroup
+// segments up to this many lookups are summed by one LPR-lane worker of the apply in
+// ascending sample order (apply_segment holds ceil(kShortSeg / LPR) samples per
+// lane), longer ones by a whole workgroup.  The same for every row geometry: the
+// sorted layout and the large-batch path cut at kShortSeg too, so a row's sum does
+// not depend on the layout, and the bucket's long list (B / kShortSeg + 4 entries)
+// holds every longer segment.  (64 / lpr for 128-B and 256-B rows summed their
+// 5..16-lookup segments in tree order, and could list more than the long list holds.)
 __host__ __device__ inline int short_seg(int lpr) {
-  return 64 / lpr < kShortSeg ? 64 / lpr : kShortSeg;
+  (void)lpr;
+  return kShortSeg;
 }
 
 // hash layout for `batch` entries (the same rule in plan and apply)

@@ -90,7 +90,10 @@ def _oracle_step(kind, spec, P, G, S, t, lr):
                            spec["weight_decay"], spec.get("bias_correction", True))
 
 
-def _run(name, dtype, rows, B, steps, has_w, F, D=16, lr=0.05, seed=0, lr_sched=None):
+def _run(name, dtype, rows, B, steps, has_w, F, D=16, lr=0.05, seed=0, lr_sched=None,
+         with_state=False):
+    """Returns (tables of the bank, the oracle's tables); ``with_state``: also the bank
+    and the oracle's optimizer state S[f] = (s0, s1)."""
     from pytorchrec_amd.embedding import gather
     spec, kind = SPECS[name]
     spec = dict(spec)
@@ -131,6 +134,8 @@ def _run(name, dtype, rows, B, steps, has_w, F, D=16, lr=0.05, seed=0, lr_sched=
         _oracle_step(kind, spec, P, G, S, s + 1, lr)
     bank.flush_optimizer()
     torch.cuda.synchronize()
+    if with_state:
+        return _table(bank, rows, F, D, has_w), P, bank, S
     return _table(bank, rows, F, D, has_w), P
 
 
