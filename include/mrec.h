@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MREC_ABI_VERSION 29
+#define MREC_ABI_VERSION 30
 #define MREC_MAX_TABLES 64      /* tables per table bank / per call */
 #define MREC_BWD_MAX_BATCH 8192  /* lookups per table per plan/apply call */
 #define MREC_BWD_HASH_MAX_BATCH 4096  /* batches up to this use the hash plan */
@@ -113,6 +113,41 @@ const char *mrec_last_error(void);
 mrec_status mrec_emb_gather_fwd(const mrec_table_bank *bank, const mrec_ids *ids, int64_t batch,
                                 void *out, mrec_dtype out_dtype, int64_t out_ld, float *w_out,
                                 int32_t *d_oob_flag, mrec_stream stream);
+
+/* pooled (multi-valued) lookups, ABI 30 */
+#define MREC_POOL_SUM 0   /* s = 1 */
+#define MREC_POOL_MEAN 1  /* s = 1 / n, n = the bag's valid count */
+#define MREC_POOL_SQRTN 2 /* s = 1 / sqrt(n): the reference's SVD++ history term (SVDPP.py:49-55) */
+#define MREC_POOL_PAD_ZERO 0     /* id 0 is padding (the reference's `iids > 0` mask, SVDPP.py:50);
+                                    a negative id is out of range, as nn.Embedding raises on it
+                                    before the mask applies */
+#define MREC_POOL_PAD_NEGATIVE 1 /* a negative id is padding, id 0 is a real row: the
+                                    pad_negative convention of mrec_ids */
+
+/*
+ * Pooled lookup (ABI 30): a field of a sample is a BAG of bag_len ids -- field f, bag
+ * b, position j at field_ptr[f][b * ids->stride + j], stride >= bag_len, every field
+ * of the call with the same bag_len -- and
+ *   out[b, f*dim + d]      = s_bf * sum_{valid j} bank[row_offset[f] + id_bfj, d]
+ *   bag_scale[b*F + f]     = s_bf   (fp32, required: the backward's per-bag factor)
+ *   w_out[b*F + f]         = s_bf * sum_{valid j} w   (when non-NULL; bank must have_w)
+ *   lookup_ids[f][b*bag_len + j] = id of a valid lookup, -1 for padding and for an
+ *                            out-of-range id (nullable; int32 [F][n_bags * bag_len]:
+ *                            the padded id view, pad_negative = 1, that the backward
+ *                            plan consumes -- built in the gather launch as
+ *                            mrec_din_gather builds its ids)
+ * The sum is fp32 in ascending position order from a -0.0f accumulator (bitwise
+ * reproducible), then one multiply by s and one rounding into out_dtype (F32 / BF16).
+ * An empty bag gives a zero row and s = 0 (the reference: 0 / sqrt(0) = NaN).  An
+ * out-of-range id sets *d_oob_flag, contributes nothing and is never dereferenced.
+ * A bank under the lazy fused Adam is read as of the last step, like every gather.
+ * Replaces implicit_i_embeddings(iids) + mask + sum + / sqrt(count), SVDPP.py:49-55.
+ */
+mrec_status mrec_emb_pool_fwd(const mrec_table_bank *bank, const mrec_ids *ids, int64_t n_bags,
+                              int32_t bag_len, int32_t pool_mode, int32_t pad_mode, void *out,
+                              mrec_dtype out_dtype, int64_t out_ld, float *w_out,
+                              float *bag_scale, int32_t *lookup_ids, int32_t *d_oob_flag,
+                              mrec_stream stream);
 
 /* flags for mrec_interact_fwd */
 #define MREC_INTERACT_FM2 1         /* add 1/2 sum_d[(sum_f v)^2 - sum_f v^2] */
@@ -472,6 +507,38 @@ mrec_status mrec_emb_bwd_apply_ex(const mrec_table_bank *bank, int64_t batch,
                                   uint64_t seed, const uint64_t *d_step, void *grad,
                                   int32_t n_reduce, const struct mrec_gemm_call_s *reduce,
                                   mrec_stream stream);
+
+/*
+ * The backward of mrec_emb_pool_fwd (ABI 30; the gradient of SVDPP.py:49-55): the
+ * arguments of mrec_emb_bwd_apply_ex / mrec_emb_bwd_large_fused_ex over batch =
+ * n_bags * bag_len lookups -- planned from the forward's lookup_ids view -- whose
+ * gradients come through a bag index: lookup i of table f takes
+ *   g_v = bag_scale[bb*F + f] * dx[bb*dx_ld + f*dim + d],  g_w = bag_scale[bb*F + f] * dw[bb]
+ * with bb = i / bag_len (one fp32 multiply; dx / dw hold one row per bag, so the
+ * bag's gradient row is never expanded to bag_len copies).  Everything else is the
+ * plain entry's: layouts and the layout rule (a plain apply's), every mrec_bwd_mode,
+ * stochastic rounding, co-launched reductions, the same segment sums -- the result is
+ * bitwise that of the plain entry over the expanded gradient.  bag_len >= 1, batch a
+ * multiple of it, bag_scale non-NULL, dfm NULL (the FM term is undefined for bags).
+ */
+mrec_status mrec_emb_bwd_apply_bag(const mrec_table_bank *bank, int64_t batch,
+                                   const void *workspace, size_t ws_bytes, const void *dx,
+                                   mrec_dtype dx_dtype, int64_t dx_ld, const float *dfm,
+                                   const float *fm_sum, const void *x0, mrec_dtype x0_dtype,
+                                   int64_t x0_ld, const float *dw, mrec_bwd_mode mode, float lr,
+                                   uint64_t seed, const uint64_t *d_step, void *grad,
+                                   int32_t n_reduce, const struct mrec_gemm_call_s *reduce,
+                                   mrec_stream stream, int32_t bag_len, const float *bag_scale);
+mrec_status mrec_emb_bwd_large_fused_bag(const mrec_table_bank *bank, const mrec_ids *ids,
+                                         int64_t batch, void *workspace, size_t ws_bytes,
+                                         int32_t *d_oob_flag, const void *dx, mrec_dtype dx_dtype,
+                                         int64_t dx_ld, const float *dfm, const float *fm_sum,
+                                         const void *x0, mrec_dtype x0_dtype, int64_t x0_ld,
+                                         const float *dw, mrec_bwd_mode mode, float lr,
+                                         uint64_t seed, const uint64_t *d_step, void *grad,
+                                         int32_t n_reduce, const struct mrec_gemm_call_s *reduce,
+                                         mrec_stream stream, int32_t bag_len,
+                                         const float *bag_scale);
 
 /*
  * mrec_emb_bwd_apply with the per-lookup gradient rows given directly instead of

@@ -20,7 +20,7 @@ import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("MREC_LIB_PATH") or os.path.join(LIB_DIR, "libmrec.so")
 
-ABI_VERSION = 29
+ABI_VERSION = 30
 MAX_TABLES = 64
 BWD_MAX_BATCH = 8192
 BWD_HASH_MAX_BATCH = 4096  # batches up to this use the hash plan (fusable into a GEMM launch)
@@ -36,6 +36,9 @@ INTERACT_FIRST_ORDER = 2
 BWD_DENSE_GRAD, BWD_SGD, BWD_SGD_SR = 0, 1, 2
 BWD_ADAGRAD, BWD_ROWWISE_ADAGRAD, BWD_ADAM = 3, 4, 5  # fused optimizers (bank.optim)
 OPT_DECOUPLED_WD, OPT_NO_BIAS_CORRECTION = 1, 2
+# pooled lookups (mrec_emb_pool_fwd)
+POOL_SUM, POOL_MEAN, POOL_SQRTN = 0, 1, 2
+POOL_PAD_ZERO, POOL_PAD_NEGATIVE = 0, 1
 
 _STATUS_NAMES = {OK: "MREC_OK", EINVAL: "MREC_EINVAL", EOOB: "MREC_EOOB", EHIP: "MREC_EHIP",
                  ERCCL: "MREC_ERCCL", ENOSPC: "MREC_ENOSPC"}
@@ -241,6 +244,8 @@ SIGNATURES = {
     "mrec_last_error": (ctypes.c_char_p, []),
     "mrec_emb_gather_fwd": (ctypes.c_int, [_bank_p, _ids_p, _i64, _vp, ctypes.c_int, _i64, _vp,
                                            _vp, _vp]),
+    "mrec_emb_pool_fwd": (ctypes.c_int, [_bank_p, _ids_p, _i64, _i32, _i32, _i32, _vp, ctypes.c_int,
+                                         _i64, _vp, _vp, _vp, _vp, _vp]),
     "mrec_interact_fwd": (ctypes.c_int, [_bank_p, _ids_p, _i64, _vp, _i32, _i64, _vp, _vp, _i32,
                                          _vp, ctypes.c_int, _i64, _i32, _vp, _vp, _vp, _vp]),
     "mrec_interact_fwd_ex": (ctypes.c_int, [_bank_p, _ids_p, _i64, _vp, _i32, _i64, _vp, _vp, _i32,
@@ -261,6 +266,10 @@ SIGNATURES = {
                                              _i64, _vp, _vp, _vp, ctypes.c_int, _i64, _vp,
                                              ctypes.c_int, _f32, ctypes.c_uint64, _vp, _vp, _i32,
                                              ctypes.POINTER(GemmCall), _vp]),
+    "mrec_emb_bwd_apply_bag": (ctypes.c_int, [_bank_p, _i64, _vp, ctypes.c_size_t, _vp, ctypes.c_int,
+                                              _i64, _vp, _vp, _vp, ctypes.c_int, _i64, _vp,
+                                              ctypes.c_int, _f32, ctypes.c_uint64, _vp, _vp, _i32,
+                                              ctypes.POINTER(GemmCall), _vp, _i32, _vp]),
     "mrec_emb_bwd_apply_given": (ctypes.c_int, [_bank_p, _i64, _vp, ctypes.c_size_t, _vp,
                                                 ctypes.c_int, _i64, _vp, _vp, _vp, ctypes.c_int,
                                                 _i64, _vp, _vp, _i64, _i64, _i64, ctypes.c_int,
@@ -330,6 +339,11 @@ SIGNATURES = {
                                                    ctypes.c_int, _i64, _vp, ctypes.c_int, _f32,
                                                    ctypes.c_uint64, _vp, _vp, _i32,
                                                    ctypes.POINTER(GemmCall), _vp]),
+    "mrec_emb_bwd_large_fused_bag": (ctypes.c_int, [_bank_p, _ids_p, _i64, _vp, ctypes.c_size_t,
+                                                    _vp, _vp, ctypes.c_int, _i64, _vp, _vp, _vp,
+                                                    ctypes.c_int, _i64, _vp, ctypes.c_int, _f32,
+                                                    ctypes.c_uint64, _vp, _vp, _i32,
+                                                    ctypes.POINTER(GemmCall), _vp, _i32, _vp]),
     "mrec_head_fwd": (ctypes.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mrec_head_bwd": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp]),
     "mrec_bce_fwd": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp]),
@@ -523,6 +537,24 @@ class IdsDesc:
         flat = buf.reshape(-1)
         d = cls([flat[f * cap:] for f in range(n_tables)], chunk=cap,
                 chunk_stride=part or n_tables * cap, pad_negative=True)
+        return d
+
+    @classmethod
+    def bags(cls, fields):
+        """Per-field bags of ids for mrec_emb_pool_fwd: [B, L] tensors of one dtype,
+        contiguous along the bag and with one common row stride (>= L), read in place."""
+        fields = list(fields)
+        t0 = fields[0]
+        for t in fields:
+            if (t.dtype != t0.dtype or t.dim() != 2 or t.shape != t0.shape or t.stride(1) != 1
+                    or t.stride(0) != t0.stride(0) or t.stride(0) < t.shape[1]):
+                raise ValueError("bags must be [B, L] tensors of one dtype and row stride, "
+                                 "contiguous along the bag")
+        d = cls.__new__(cls)
+        d.tensors = fields
+        d._ptrs = (ctypes.c_void_p * len(fields))(*[t.data_ptr() for t in fields])
+        d.struct = Ids(ctypes.cast(d._ptrs, ctypes.POINTER(ctypes.c_void_p)),
+                       dtype_code(t0.dtype), int(t0.stride(0)), 0, 0, 0)
         return d
 
     def ref(self):

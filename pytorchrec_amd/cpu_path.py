@@ -53,6 +53,38 @@ def gather(bank, ids, out_dtype, with_w: bool):
     return v
 
 
+def pooled_gather(bank, ids, mode: str, pad: str, out_dtype, with_w: bool):
+    """embedding -> mask -> sum over the bag -> scale (SVDPP.py:49-55), per field; the
+    scale is 1, 1/n or 1/sqrt(n) (n = valid count), 0 for an empty bag."""
+    w = _weight(bank)
+    vs, ws = [], []
+    for f, t in enumerate(ids):
+        t = t.long()
+        B, L = t.shape
+        n = bank.category_nums[f]
+        valid = t > 0 if pad == "zero" else t >= 0
+        if bool(((t >= n) | ((t < 0) if pad == "zero" else torch.zeros_like(valid))).any()):
+            raise IndexError("index out of range in self")
+        safe = torch.where(valid, t, torch.zeros_like(t)) + bank.row_offset[f]
+        rows = w.index_select(0, safe.reshape(-1)).reshape(B, L, -1).float()
+        m = valid.float()
+        cnt = m.sum(dim=1).double()
+        if mode == "sum":
+            scale = (cnt > 0).double()
+        elif mode == "mean":
+            scale = torch.where(cnt > 0, 1.0 / cnt.clamp(min=1.0), torch.zeros_like(cnt))
+        else:
+            scale = torch.where(cnt > 0, 1.0 / cnt.clamp(min=1.0).sqrt(), torch.zeros_like(cnt))
+        pooled = (rows * m.unsqueeze(-1)).sum(dim=1) * scale.float().unsqueeze(-1)
+        vs.append(pooled[:, :bank.dim])
+        if with_w:
+            ws.append(pooled[:, bank.dim])
+    v = torch.cat(vs, dim=1).to(out_dtype)
+    if with_w:
+        return v, torch.stack(ws, dim=1)
+    return v
+
+
 def fm2(v: torch.Tensor) -> torch.Tensor:
     s = v.sum(dim=1)
     return 0.5 * (s * s - (v * v).sum(dim=1)).sum(dim=-1)

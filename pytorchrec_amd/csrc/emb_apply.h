@@ -50,7 +50,29 @@ struct ApplyArgs {
   // mrec_emb_bwd_apply_wire_sgd): a device-resident SgdArgs (optim_common.h)
   const struct SgdArgs *sgd;
   int sgd_blocks;
+  // bag indirection (ABI 30, mrec_emb_bwd_apply_bag / _large_fused_bag): the lookups
+  // are the bag_len positions of pooled bags, lookup i of table f belongs to bag
+  // bb = i / bag and its gradient is bag_scale[bb * g_F + f] * (dx | dw)[bb]: the
+  // bag's gradient row is read through the index, never expanded.  0 = off.
+  int bag;
+  const float *bag_scale;
 };
+
+// lookup i -> its bag (i < 2^31: the entry points check batch), and the bag's scale
+__device__ __forceinline__ float bag_index(const ApplyArgs &a, int64_t &b, int f) {
+  b = static_cast<int64_t>(static_cast<uint32_t>(b) / static_cast<uint32_t>(a.bag));
+  return a.bag_scale[b * a.g_F + f];
+}
+// one fp32 multiply per element (never contracted into the segment sum's add)
+template <int EPL>
+__device__ __forceinline__ void bag_scale_grad(float bs, bool v_lane, float *g) {
+  if (v_lane) {
+#pragma unroll
+    for (int j = 0; j < EPL; ++j) g[j] = __fmul_rn(bs, g[j]);
+  } else {
+    g[0] = __fmul_rn(bs, g[0]);
+  }
+}
 
 // a given gradient from a wire record (4-B aligned rows: records are not 16-B).
 // An entry past its part's cap_rows records had its record clipped by the sender
@@ -111,8 +133,10 @@ __device__ __forceinline__ void load_bf16xN(const uint16_t *p, float *v) {
   }
 }
 
-// gradient of lookup (b, f) for this lane's EPL elements (w lane: g[0])
-template <int EPL>
+// gradient of lookup (b, f) for this lane's EPL elements (w lane: g[0]).  BAG: the
+// bag indirection, a template flag instantiated only by the bag entry points, so
+// every other kernel compiles exactly as it would without it
+template <int EPL, bool BAG = false>
 __device__ __forceinline__ void lookup_grad(const ApplyArgs &a, int64_t b, int f, int D, int e0,
                                             bool v_lane, bool w_lane, float *g) {
 #pragma unroll
@@ -130,6 +154,8 @@ __device__ __forceinline__ void lookup_grad(const ApplyArgs &a, int64_t b, int f
       g[0] = go[D];
     return;
   }
+  float bs = 0.f;
+  if constexpr (BAG) bs = bag_index(a, b, f);  // b becomes the bag (dfm is NULL)
   if (v_lane) {
     // the same arithmetic as mrec_shard_lookup_grad, so sharded and unsharded
     // updates agree
@@ -154,12 +180,13 @@ __device__ __forceinline__ void lookup_grad(const ApplyArgs &a, int64_t b, int f
   } else if (w_lane && a.dw) {
     g[0] = a.dw[b];
   }
+  if constexpr (BAG) bag_scale_grad<EPL>(bs, v_lane, g);
 }
 
 // gradient of lookup (b, f) with the row's current values v (this lane's EPL
 // elements, bank dtype widened) for the FM term: the hash-layout apply reads the
 // row it updates anyway, so the gathered rows are not re-read from x0
-template <int EPL>
+template <int EPL, bool BAG = false>
 __device__ __forceinline__ void lookup_grad_v(const ApplyArgs &a, int64_t b, int f, int D, int e0,
                                               bool v_lane, bool w_lane, const float *v, float *g) {
 #pragma unroll
@@ -177,6 +204,8 @@ __device__ __forceinline__ void lookup_grad_v(const ApplyArgs &a, int64_t b, int
       g[0] = go[D];
     return;
   }
+  float bs = 0.f;
+  if constexpr (BAG) bs = bag_index(a, b, f);  // b becomes the bag (dfm is NULL)
   if (v_lane) {
     const int64_t col = static_cast<int64_t>(f) * D + e0;
     if (a.dx) {
@@ -195,24 +224,25 @@ __device__ __forceinline__ void lookup_grad_v(const ApplyArgs &a, int64_t b, int
   } else if (w_lane && a.dw) {
     g[0] = a.dw[b];
   }
+  if constexpr (BAG) bag_scale_grad<EPL>(bs, v_lane, g);
 }
 
-template <int EPL>
+template <int EPL, bool BAG = false>
 __device__ __forceinline__ void add_lookup_grad_v(const ApplyArgs &a, int64_t b, int f, int D,
                                                   int e0, bool v_lane, bool w_lane, const float *v,
                                                   float *acc) {
   float g[EPL];
-  lookup_grad_v<EPL>(a, b, f, D, e0, v_lane, w_lane, v, g);
+  lookup_grad_v<EPL, BAG>(a, b, f, D, e0, v_lane, w_lane, v, g);
 #pragma unroll
   for (int j = 0; j < EPL; ++j) acc[j] += g[j];
 }
 
 // per-lookup gradient first, then one add into the segment sum
-template <int EPL>
+template <int EPL, bool BAG = false>
 __device__ __forceinline__ void add_lookup_grad(const ApplyArgs &a, int64_t b, int f, int D,
                                                 int e0, bool v_lane, bool w_lane, float *acc) {
   float g[EPL];
-  lookup_grad<EPL>(a, b, f, D, e0, v_lane, w_lane, g);
+  lookup_grad<EPL, BAG>(a, b, f, D, e0, v_lane, w_lane, g);
 #pragma unroll
   for (int j = 0; j < EPL; ++j) acc[j] += g[j];
 }

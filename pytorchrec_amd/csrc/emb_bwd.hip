@@ -250,7 +250,7 @@ struct HotSeg {
 
   // samples: perm[0, sn); v: the row's values for the FM term (nullptr: take v
   // from x0, the sorted layout's rule)
-  template <bool ROW_V, int MODE = -1>
+  template <bool ROW_V, int MODE = -1, bool BAG = false>
   __device__ __forceinline__ void run(const BankArgs &bank, const ApplyArgs &a, int f, int64_t row,
                                       const int32_t *perm, int sn, int64_t B, const float *v,
                                       int worker, int e0, bool v_lane, bool w_lane, bool live) {
@@ -316,9 +316,9 @@ struct HotSeg {
           for (int u = 0; u < KB; ++u) {
             const int b = bs[u] < 0 ? bs[0] : bs[u];  // (a repeat of a valid one; not added)
             if constexpr (ROW_V)
-              lookup_grad_v<EPL>(a, b, f, D, e0, v_lane, w_lane, v, g[u]);
+              lookup_grad_v<EPL, BAG>(a, b, f, D, e0, v_lane, w_lane, v, g[u]);
             else
-              lookup_grad<EPL>(a, b, f, D, e0, v_lane, w_lane, g[u]);
+              lookup_grad<EPL, BAG>(a, b, f, D, e0, v_lane, w_lane, g[u]);
           }
 #pragma unroll
           for (int u = 0; u < KB; ++u)
@@ -373,7 +373,7 @@ struct HotSeg {
 #endif
 constexpr int kSegBatch = MREC_SEG_BATCH;  // gradient loads in flight per segment step
 
-template <typename T, int LPR, int MODE>
+template <typename T, int LPR, int MODE, bool BAG = false>
 __device__ __forceinline__ void apply_segment(const BankArgs &bank, const ApplyArgs &a,
                                               const BucketWs &t, int f, int64_t toff_f,
                                               const int4 d, int l, int e0, bool v_lane,
@@ -403,8 +403,8 @@ __device__ __forceinline__ void apply_segment(const BankArgs &bank, const ApplyA
   if (n == 2) {  // both lookups in the descriptor: ascending b, loads in flight together
     if (live) {
       float g0[EPL], g1[EPL];
-      lookup_grad_v<EPL>(a, min(d.z, d.w), f, D, e0, v_lane, w_lane, v, g0);
-      lookup_grad_v<EPL>(a, max(d.z, d.w), f, D, e0, v_lane, w_lane, v, g1);
+      lookup_grad_v<EPL, BAG>(a, min(d.z, d.w), f, D, e0, v_lane, w_lane, v, g0);
+      lookup_grad_v<EPL, BAG>(a, max(d.z, d.w), f, D, e0, v_lane, w_lane, v, g1);
 #pragma unroll
       for (int j = 0; j < EPL; ++j) acc[j] = (acc[j] + g0[j]) + g1[j];
     }
@@ -433,7 +433,7 @@ __device__ __forceinline__ void apply_segment(const BankArgs &bank, const ApplyA
       for (int k = 0; k < kSegBatch; ++k) {
 #pragma unroll
         for (int j = 0; j < EPL; ++j) g[k][j] = 0.f;
-        if (live && sb[k] != INT_MAX) lookup_grad_v<EPL>(a, sb[k], f, D, e0, v_lane, w_lane, v, g[k]);
+        if (live && sb[k] != INT_MAX) lookup_grad_v<EPL, BAG>(a, sb[k], f, D, e0, v_lane, w_lane, v, g[k]);
       }
 #pragma unroll
       for (int k = 0; k < kSegBatch; ++k)
@@ -445,7 +445,7 @@ __device__ __forceinline__ void apply_segment(const BankArgs &bank, const ApplyA
   row_update<T, LPR, MODE>(bank, a, grow, e0, v_lane, w_lane, live, acc, raw);
 }
 
-template <typename T, int LPR, int MODE, bool KC>
+template <typename T, int LPR, int MODE, bool KC, bool BAG = false>
 __global__ __launch_bounds__(256, MREC_APPLY_WAVES) void apply_hash_kernel(BankArgs bank, int64_t B,
                                                                            const void *ws, ApplyArgs a,
                                                                            int seg_blocks, int sm_blocks,
@@ -500,7 +500,7 @@ __global__ __launch_bounds__(256, MREC_APPLY_WAVES) void apply_hash_kernel(BankA
       if (s < nseg) {
         const int4 d = s0 == 0 ? dpre : t.desc[s];
         if (d.y <= sshort)
-          apply_segment<T, LPR, MODE>(bank, a, t, f, toff_f, d, l, e0, v_lane, w_lane, live);
+          apply_segment<T, LPR, MODE, BAG>(bank, a, t, f, toff_f, d, l, e0, v_lane, w_lane, live);
       }
     }
     return;
@@ -527,7 +527,7 @@ __global__ __launch_bounds__(256, MREC_APPLY_WAVES) void apply_hash_kernel(BankA
           vr = adam_current<T>(bank, toff_f + d.x, e0, EPL, vr, *bank.adam.d_t - 1);
         Vec<T>::to_f32(vr, v);
       }
-      hot.template run<true, MODE>(bank, a, f, d.x, t.perm + d.z, d.y, B, v, worker, e0, v_lane,
+      hot.template run<true, MODE, BAG>(bank, a, f, d.x, t.perm + d.z, d.y, B, v, worker, e0, v_lane,
                                    w_lane, live);
     }
     return;
@@ -547,7 +547,7 @@ __global__ __launch_bounds__(256, MREC_APPLY_WAVES) void apply_hash_kernel(BankA
   float dfm_c = 0.f;
 #pragma unroll
   for (int j = 0; j < EPL; ++j) gdx[j] = fs[j] = 0.f;
-  const bool pre = live && !a.g_occ && !a.g_rec;
+  const bool pre = !BAG && live && !a.g_occ && !a.g_rec;  // (bags: add_lookup_grad_v)
   if (pre) {
     if (v_lane) {
       const int64_t col = static_cast<int64_t>(f) * D + e0;
@@ -590,7 +590,7 @@ __global__ __launch_bounds__(256, MREC_APPLY_WAVES) void apply_hash_kernel(BankA
 #pragma unroll
     for (int j = 0; j < EPL; ++j) acc[j] += gdx[j];
   } else if (live) {
-    add_lookup_grad_v<EPL>(a, b, f, D, e0, v_lane, w_lane, v, acc);
+    add_lookup_grad_v<EPL, BAG>(a, b, f, D, e0, v_lane, w_lane, v, acc);
   }
   row_update<T, LPR, MODE>(bank, a, grow, e0, v_lane, w_lane, live, acc, raw);
 }
@@ -602,7 +602,7 @@ __global__ __launch_bounds__(256, MREC_APPLY_WAVES) void apply_hash_kernel(BankA
 // F * seg_blocks segment blocks (table f = blk / seg_blocks), then the
 // co-launched reductions.
 // ---------------------------------------------------------------------------
-template <typename T, int LPR>
+template <typename T, int LPR, bool BAG = false>
 __global__ __launch_bounds__(256, 6) void apply_kernel(BankArgs bank, int64_t B, const void *ws,
                                                        ApplyArgs a, int seg_blocks,
                                                        int apply_blocks, CoReduce co) {
@@ -653,7 +653,7 @@ __global__ __launch_bounds__(256, 6) void apply_kernel(BankArgs bank, int64_t B,
 #pragma unroll
     for (int j = 0; j < EPL; ++j) acc[j] = 0.f;
     if (live)
-      for (int j = 0; j < n; ++j) add_lookup_grad<EPL>(a, t.perm[s0 + j], f, D, e0, v_lane, w_lane, acc);
+      for (int j = 0; j < n; ++j) add_lookup_grad<EPL, BAG>(a, t.perm[s0 + j], f, D, e0, v_lane, w_lane, acc);
     row_update<T, LPR, -1>(bank, a, bank.row_offset[f] + row, e0, v_lane, w_lane, live, acc, raw);
   }
   __syncthreads();
@@ -666,7 +666,7 @@ __global__ __launch_bounds__(256, 6) void apply_kernel(BankArgs bank, int64_t B,
     const int lrow = t.uniq[uu];
     const int ls0 = t.seg[uu];
     const int sn = t.seg[uu + 1] - ls0;
-    hot.template run<false>(bank, a, f, lrow, t.perm + ls0, sn, B, nullptr, worker, e0, v_lane,
+    hot.template run<false, -1, BAG>(bank, a, f, lrow, t.perm + ls0, sn, B, nullptr, worker, e0, v_lane,
                             w_lane, live);
   }
 }
@@ -857,6 +857,10 @@ struct GivenWire {  // mrec_emb_bwd_apply_wire: given gradients as wire records
   const int32_t *pref;
   int64_t cap_rows;
 };
+struct BagGrad {  // mrec_emb_bwd_apply_bag: the lookups are the positions of pooled bags
+  int32_t bag_len;
+  const float *scale;
+};
 struct RecOut {  // mrec_emb_bwd_apply_rec: DENSE_GRAD sums into wire records
   void *wire;
   int rec_dw;
@@ -874,7 +878,8 @@ static mrec_status apply_impl(const mrec_table_bank *bank, int64_t batch, const 
                               const uint64_t *d_step, void *grad, int32_t n_reduce,
                               const mrec_gemm_call *reduce, mrec_stream stream,
                               const GivenWire *gw = nullptr, const RecOut *ro = nullptr,
-                              const void *sgd_table = nullptr, int32_t sgd_blocks = 0);
+                              const void *sgd_table = nullptr, int32_t sgd_blocks = 0,
+                              const BagGrad *bag = nullptr);
 
 extern "C" {
 
@@ -900,6 +905,24 @@ mrec_status mrec_emb_bwd_apply_ex(const mrec_table_bank *bank, int64_t batch,
   return apply_impl(bank, batch, workspace, ws_bytes, dx, dx_dtype, dx_ld, dfm, fm_sum, x0,
                     x0_dtype, x0_ld, dw, nullptr, 0, 0, 0, mode, lr, seed, d_step, grad, n_reduce,
                     reduce, stream);
+}
+
+mrec_status mrec_emb_bwd_apply_bag(const mrec_table_bank *bank, int64_t batch,
+                                   const void *workspace, size_t ws_bytes, const void *dx,
+                                   mrec_dtype dx_dtype, int64_t dx_ld, const float *dfm,
+                                   const float *fm_sum, const void *x0, mrec_dtype x0_dtype,
+                                   int64_t x0_ld, const float *dw, mrec_bwd_mode mode, float lr,
+                                   uint64_t seed, const uint64_t *d_step, void *grad,
+                                   int32_t n_reduce, const mrec_gemm_call *reduce,
+                                   mrec_stream stream, int32_t bag_len, const float *bag_scale) {
+  MREC_CHECK_ARG(bag_len >= 1, "bag_len < 1");
+  MREC_CHECK_ARG(batch >= 0 && batch % bag_len == 0, "batch is not a multiple of bag_len");
+  MREC_CHECK_ARG(bag_scale != nullptr, "bag_scale is NULL");
+  MREC_CHECK_ARG(dfm == nullptr, "the FM term is undefined for bags (dfm must be NULL)");
+  const BagGrad bg{bag_len, bag_scale};
+  return apply_impl(bank, batch, workspace, ws_bytes, dx, dx_dtype, dx_ld, dfm, fm_sum, x0,
+                    x0_dtype, x0_ld, dw, nullptr, 0, 0, 0, mode, lr, seed, d_step, grad, n_reduce,
+                    reduce, stream, nullptr, nullptr, nullptr, 0, &bg);
 }
 
 mrec_status mrec_emb_bwd_apply_given(const mrec_table_bank *bank, int64_t batch,
@@ -978,7 +1001,7 @@ static mrec_status apply_impl(const mrec_table_bank *bank, int64_t batch, const 
                               const uint64_t *d_step, void *grad, int32_t n_reduce,
                               const mrec_gemm_call *reduce, mrec_stream stream,
                               const GivenWire *gw, const RecOut *ro, const void *sgd_table,
-                              int32_t sgd_blocks) {
+                              int32_t sgd_blocks, const BagGrad *bag) {
   BankArgs ba;
   int eb, lpr;
   mrec_status st = make_bank_args(bank, &ba, &eb, &lpr);
@@ -995,6 +1018,7 @@ static mrec_status apply_impl(const mrec_table_bank *bank, int64_t batch, const 
   const bool hash = hash_layout(batch, g_occ != nullptr || gw != nullptr);
   if ((st = ws_layout_check(workspace, hash ? kLayoutHash : kLayoutSorted, batch, ba.n_tables,
                             gw ? "mrec_emb_bwd_apply_wire"
+                               : bag ? "mrec_emb_bwd_apply_bag"
                                : ro ? "mrec_emb_bwd_apply_rec"
                                     : g_occ ? "mrec_emb_bwd_apply_given" : "mrec_emb_bwd_apply")) !=
       MREC_OK)
@@ -1081,6 +1105,8 @@ static mrec_status apply_impl(const mrec_table_bank *bank, int64_t batch, const 
                  "sgd_blocks > 0 needs the table");
   a.sgd = static_cast<const SgdArgs *>(sgd_table);
   a.sgd_blocks = sgd_blocks;
+  a.bag = bag ? bag->bag_len : 0;  // (dx / dw hold batch / bag_len rows: one per bag)
+  a.bag_scale = bag ? bag->scale : nullptr;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int wpb = 256 / lpr;
   // hash layout (batch <= kHashMaxKeys or an exchange view, see mrec_emb_bwd_plan):
@@ -1100,7 +1126,7 @@ static mrec_status apply_impl(const mrec_table_bank *bank, int64_t batch, const 
   MREC_CHECK_ARG(sgd_blocks == 0 || hash, "SGD tiles ride in the hash-layout apply only");
   if (apply_blocks + co_blocks == 0) return MREC_OK;  // (batch 0 still runs the reductions)
   const dim3 grid(static_cast<unsigned>(apply_blocks + co_blocks));
-  const KClock kc = hash ? kclock_take() : KClock{nullptr, 0};
+  const KClock kc = hash && !bag ? kclock_take() : KClock{nullptr, 0};  // (bags: unclocked)
 #define MREC_AKM(T, L, M)                                                                         \
   do {                                                                                            \
     if (kc.buf)                                                                                   \
@@ -1121,23 +1147,59 @@ static mrec_status apply_impl(const mrec_table_bank *bank, int64_t batch, const 
       apply_kernel<T, L><<<grid, 256, 0, s>>>(ba, batch, workspace, a, seg_blocks, apply_blocks, \
                                               co);                                               \
   } while (0)
-  if (bank->dtype == MREC_BF16) {
+  // the bag-indirection instantiations (mrec_emb_bwd_apply_bag only, unclocked):
+  // dispatched after every other kernel of the file, whose layout they leave alone
+#define MREC_BKM(T, L, M)                                      \
+  apply_hash_kernel<T, L, M, false, true><<<grid, 256, 0, s>>>( \
+      ba, batch, workspace, a, seg_blocks, static_cast<int>(sm_blocks), co, kc)
+#define MREC_BK(T, L)                                                                          \
+  do {                                                                                         \
+    if (hash) {                                                                                \
+      if (mode == MREC_BWD_SGD) MREC_BKM(T, L, MREC_BWD_SGD);                                  \
+      else if (mode == MREC_BWD_SGD_SR) MREC_BKM(T, L, MREC_BWD_SGD_SR);                       \
+      else if (mode == MREC_BWD_DENSE_GRAD) MREC_BKM(T, L, MREC_BWD_DENSE_GRAD);               \
+      else MREC_BKM(T, L, -1);                                                                 \
+    } else                                                                                     \
+      apply_kernel<T, L, true><<<grid, 256, 0, s>>>(ba, batch, workspace, a, seg_blocks,       \
+                                                    apply_blocks, co);                         \
+  } while (0)
+  if (!bag) {
+    if (bank->dtype == MREC_BF16) {
+      switch (lpr) {
+        case 1: MREC_AK(uint16_t, 1); break;
+        case 2: MREC_AK(uint16_t, 2); break;
+        case 4: MREC_AK(uint16_t, 4); break;
+        case 8: MREC_AK(uint16_t, 8); break;
+        default: MREC_AK(uint16_t, 16); break;
+      }
+    } else {
+      switch (lpr) {
+        case 1: MREC_AK(float, 1); break;
+        case 2: MREC_AK(float, 2); break;
+        case 4: MREC_AK(float, 4); break;
+        case 8: MREC_AK(float, 8); break;
+        default: MREC_AK(float, 16); break;
+      }
+    }
+  } else if (bank->dtype == MREC_BF16) {
     switch (lpr) {
-      case 1: MREC_AK(uint16_t, 1); break;
-      case 2: MREC_AK(uint16_t, 2); break;
-      case 4: MREC_AK(uint16_t, 4); break;
-      case 8: MREC_AK(uint16_t, 8); break;
-      default: MREC_AK(uint16_t, 16); break;
+      case 1: MREC_BK(uint16_t, 1); break;
+      case 2: MREC_BK(uint16_t, 2); break;
+      case 4: MREC_BK(uint16_t, 4); break;
+      case 8: MREC_BK(uint16_t, 8); break;
+      default: MREC_BK(uint16_t, 16); break;
     }
   } else {
     switch (lpr) {
-      case 1: MREC_AK(float, 1); break;
-      case 2: MREC_AK(float, 2); break;
-      case 4: MREC_AK(float, 4); break;
-      case 8: MREC_AK(float, 8); break;
-      default: MREC_AK(float, 16); break;
+      case 1: MREC_BK(float, 1); break;
+      case 2: MREC_BK(float, 2); break;
+      case 4: MREC_BK(float, 4); break;
+      case 8: MREC_BK(float, 8); break;
+      default: MREC_BK(float, 16); break;
     }
   }
+#undef MREC_BK
+#undef MREC_BKM
 #undef MREC_AK
 #undef MREC_AKM
   return launch_status("mrec_emb_bwd_apply");

@@ -754,7 +754,7 @@ __global__ __launch_bounds__(256) void bk_group_kernel(LgWs w, int G, int lognb,
 // ---- apply -------------------------------------------------------------------
 // pass 1 over the long segments' chunks: max |g| per segment (bits of a
 // non-negative float order like the float)
-template <typename T, int LPR>
+template <typename T, int LPR, bool BAG = false>
 __device__ __forceinline__ void lg_longmax_chunk(BankArgs bank, LgWs w, ApplyArgs a, int j) {
   constexpr int EPL = Vec<T>::EPL;
   constexpr int WPB = 256 / LPR;
@@ -772,7 +772,7 @@ __device__ __forceinline__ void lg_longmax_chunk(BankArgs bank, LgWs w, ApplyArg
     if (v_lane || w_lane)
       for (int i = s0 + worker; i < s1; i += WPB) {
         float g[EPL];
-        lookup_grad<EPL>(a, w.perm[i], f, D, e0, v_lane, w_lane, g);
+        lookup_grad<EPL, BAG>(a, w.perm[i], f, D, e0, v_lane, w_lane, g);
 #pragma unroll
         for (int q = 0; q < EPL; ++q) m = fmaxf(m, fabsf(g[q]));
       }
@@ -782,11 +782,11 @@ __device__ __forceinline__ void lg_longmax_chunk(BankArgs bank, LgWs w, ApplyArg
   }
 }
 
-template <typename T, int LPR>
+template <typename T, int LPR, bool BAG = false>
 __device__ __forceinline__ void lg_longmax_body(BankArgs bank, int64_t n, LgWs w,
                                                          ApplyArgs a) {
   const int nchunks = w.hdr[2];
-  for (int j = blockIdx.x; j < nchunks; j += gridDim.x) lg_longmax_chunk<T, LPR>(bank, w, a, j);
+  for (int j = blockIdx.x; j < nchunks; j += gridDim.x) lg_longmax_chunk<T, LPR, BAG>(bank, w, a, j);
 }
 
 // fixed-point scale of long segment L: sum of len terms of |x| <= max stays < 2^62
@@ -801,7 +801,7 @@ __device__ __forceinline__ int lg_scale(float mx, int len) {
 
 // pass 2: fixed-point chunk sums added into the segment's int64 accumulator
 // (workgroup-uniform: one chunk per call, LDS reduction with barriers)
-template <typename T, int LPR>
+template <typename T, int LPR, bool BAG = false>
 __device__ __forceinline__ void lg_longacc_chunk(BankArgs bank, LgWs w, ApplyArgs a, int stride,
                                                  int j) {
   constexpr int EPL = Vec<T>::EPL;
@@ -824,7 +824,7 @@ __device__ __forceinline__ void lg_longacc_chunk(BankArgs bank, LgWs w, ApplyArg
     if (v_lane || w_lane)
       for (int i = s0 + worker; i < s1; i += WPB) {
         float g[EPL];
-        lookup_grad<EPL>(a, w.perm[i], f, D, e0, v_lane, w_lane, g);
+        lookup_grad<EPL, BAG>(a, w.perm[i], f, D, e0, v_lane, w_lane, g);
 #pragma unroll
         for (int q = 0; q < EPL; ++q) acc[q] += llrint(ldexp(static_cast<double>(g[q]), S));
       }
@@ -849,12 +849,12 @@ __device__ __forceinline__ void lg_longacc_chunk(BankArgs bank, LgWs w, ApplyArg
   }
 }
 
-template <typename T, int LPR>
+template <typename T, int LPR, bool BAG = false>
 __device__ __forceinline__ void lg_longacc_body(BankArgs bank, int64_t n, LgWs w,
                                                          ApplyArgs a, int stride) {
   const int nchunks = w.hdr[2];
   for (int j = blockIdx.x; j < nchunks; j += gridDim.x)
-    lg_longacc_chunk<T, LPR>(bank, w, a, stride, j);
+    lg_longacc_chunk<T, LPR, BAG>(bank, w, a, stride, j);
 }
 
 // one update per unique row.  A wave takes 64 / LPR consecutive unique rows, one
@@ -865,7 +865,7 @@ __device__ __forceinline__ void lg_longacc_body(BankArgs bank, int64_t n, LgWs w
 // longer one from the chunked kernels' accumulator.
 // (the unique rows [blk * WPB, (blk + 1) * WPB): wave wid takes the WPW from
 // blk * WPB + wid * WPW; a.seed already advanced by the step counter)
-template <typename T, int LPR>
+template <typename T, int LPR, bool BAG = false>
 __device__ __forceinline__ void lg_apply_block(BankArgs bank, LgWs w, ApplyArgs a, int stride,
                                                int blk) {
   constexpr int EPL = Vec<T>::EPL;
@@ -914,7 +914,7 @@ __device__ __forceinline__ void lg_apply_block(BankArgs bank, LgWs w, ApplyArgs 
         bitonic_sort<16>(r);
 #pragma unroll
       for (int j = 0; j < kLgShort; ++j)
-        if (j < len) add_lookup_grad<EPL>(a, r[j], f, D, e0, v_lane, w_lane, acc);
+        if (j < len) add_lookup_grad<EPL, BAG>(a, r[j], f, D, e0, v_lane, w_lane, acc);
     }
     // medium segments: the whole wave, one at a time (wave-uniform loop)
     uint64_t med = __ballot(l == 0 && len > kLgShort && L < 0);
@@ -927,7 +927,7 @@ __device__ __forceinline__ void lg_apply_block(BankArgs bank, LgWs w, ApplyArgs 
 #pragma unroll 1
         for (int j = wk; j < mlen; j += WPW) {
           float g[EPL];
-          lookup_grad<EPL>(a, w.perm[ms + j], mf, D, e0, v_lane, w_lane, g);
+          lookup_grad<EPL, BAG>(a, w.perm[ms + j], mf, D, e0, v_lane, w_lane, g);
 #pragma unroll
           for (int q = 0; q < EPL; ++q) m = fmaxf(m, fabsf(g[q]));
         }
@@ -942,7 +942,7 @@ __device__ __forceinline__ void lg_apply_block(BankArgs bank, LgWs w, ApplyArgs 
 #pragma unroll 1
         for (int j = wk; j < mlen; j += WPW) {
           float g[EPL];
-          lookup_grad<EPL>(a, w.perm[ms + j], mf, D, e0, v_lane, w_lane, g);
+          lookup_grad<EPL, BAG>(a, w.perm[ms + j], mf, D, e0, v_lane, w_lane, g);
 #pragma unroll
           for (int q = 0; q < EPL; ++q) sa[q] += llrint(ldexp(static_cast<double>(g[q]), S));
         }
@@ -963,32 +963,32 @@ __device__ __forceinline__ void lg_apply_block(BankArgs bank, LgWs w, ApplyArgs 
   }
 }
 
-template <typename T, int LPR>
+template <typename T, int LPR, bool BAG = false>
 __device__ __forceinline__ void lg_apply_body(BankArgs bank, int64_t n, LgWs w,
                                                        ApplyArgs a, int stride) {
   constexpr int WPB = 256 / LPR;
   if (a.d_step) a.seed += *a.d_step * 0x9e3779b97f4a7c15ull;
   const int nblk = (w.hdr[0] + WPB - 1) / WPB;
   for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x)
-    lg_apply_block<T, LPR>(bank, w, a, stride, blk);
+    lg_apply_block<T, LPR, BAG>(bank, w, a, stride, blk);
 }
 
-template <typename T, int LPR>
+template <typename T, int LPR, bool BAG = false>
 __global__ __launch_bounds__(256) void lg_longmax_kernel(BankArgs bank, int64_t n, LgWs w,
                                                          ApplyArgs a) {
-  lg_longmax_body<T, LPR>(bank, n, w, a);
+  lg_longmax_body<T, LPR, BAG>(bank, n, w, a);
 }
 
-template <typename T, int LPR>
+template <typename T, int LPR, bool BAG = false>
 __global__ __launch_bounds__(256) void lg_longacc_kernel(BankArgs bank, int64_t n, LgWs w,
                                                          ApplyArgs a, int stride) {
-  lg_longacc_body<T, LPR>(bank, n, w, a, stride);
+  lg_longacc_body<T, LPR, BAG>(bank, n, w, a, stride);
 }
 
-template <typename T, int LPR>
+template <typename T, int LPR, bool BAG = false>
 __global__ __launch_bounds__(256) void lg_apply_kernel(BankArgs bank, int64_t n, LgWs w,
                                                        ApplyArgs a, int stride) {
-  lg_apply_body<T, LPR>(bank, n, w, a, stride);
+  lg_apply_body<T, LPR, BAG>(bank, n, w, a, stride);
 }
 
 // The fused path's huge segments (> kLgHuge lookups of one row): max |g|, the
@@ -1021,7 +1021,7 @@ __device__ __forceinline__ bool lg_wait_done(int32_t *ctr, int target, int bound
   return true;
 }
 
-template <typename T, int LPR>
+template <typename T, int LPR, bool BAG = false>
 __global__ __launch_bounds__(256) void lg_huge_kernel(BankArgs bank, int64_t n, LgWs w,
                                                       ApplyArgs a, int stride, int stall,
                                                       int bound) {
@@ -1050,11 +1050,11 @@ __global__ __launch_bounds__(256) void lg_huge_kernel(BankArgs bank, int64_t n, 
       seen = ph;
     }
     if (ph == 0)
-      lg_longmax_chunk<T, LPR>(bank, w, a, it);
+      lg_longmax_chunk<T, LPR, BAG>(bank, w, a, it);
     else if (ph == 1)
-      lg_longacc_chunk<T, LPR>(bank, w, a, stride, it - nc);
+      lg_longacc_chunk<T, LPR, BAG>(bank, w, a, stride, it - nc);
     else
-      lg_apply_block<T, LPR>(bank, w, a, stride, it - 2 * nc);
+      lg_apply_block<T, LPR, BAG>(bank, w, a, stride, it - 2 * nc);
     if (ph < 2) {  // publish this item's atomics / stores, then count it done
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
@@ -1077,7 +1077,7 @@ __global__ __launch_bounds__(256) void lg_huge_kernel(BankArgs bank, int64_t n, 
 // go to the lists, indexed by their long slot, for the chunked kernels that follow.
 constexpr int kBkLdsPerm = 4096;  // a bucket's placed lookups stay in LDS up to this
 
-template <typename T, int LPR>
+template <typename T, int LPR, bool BAG = false>
 __global__ __launch_bounds__(256) void bk_apply_kernel(BankArgs bank, LgWs w, ApplyArgs a, int G,
                                                        int lognb, CoReduce co) {
   __shared__ uint32_t key[kBkSlots];
@@ -1234,7 +1234,7 @@ __global__ __launch_bounds__(256) void bk_apply_kernel(BankArgs bank, LgWs w, Ap
       // waited for each load in turn
       bool fast = false;
       if constexpr (EPL == 8)
-        fast = v_lane && !a.g_rec && !a.g_occ && !a.dfm && a.dx && a.dx_bf16;
+        fast = v_lane && !BAG && !a.g_rec && !a.g_occ && !a.dfm && a.dx && a.dx_bf16;
       if (fast) {
         const uint16_t *dxb = static_cast<const uint16_t *>(a.dx) + static_cast<int64_t>(f) * D + e0;
 #pragma unroll
@@ -1260,7 +1260,7 @@ __global__ __launch_bounds__(256) void bk_apply_kernel(BankArgs bank, LgWs w, Ap
       } else {
 #pragma unroll
         for (int j = 0; j < kLgShort; ++j)
-          if (j < len) add_lookup_grad<EPL>(a, rr[j], f, D, e0, v_lane, w_lane, acc);
+          if (j < len) add_lookup_grad<EPL, BAG>(a, rr[j], f, D, e0, v_lane, w_lane, acc);
       }
     }
     row_update<T, LPR, -1>(bank, a, grow, e0, v_lane, w_lane, live, acc, raw);
@@ -1270,7 +1270,7 @@ __global__ __launch_bounds__(256) void bk_apply_kernel(BankArgs bank, LgWs w, Ap
   // use); the max and the fixed-point sums do not depend on the order (DIN's category
   // table puts all of its rows here, ~130 lookups each at C4)
   bool mfast = false;
-  if constexpr (EPL == 8) mfast = v_lane && !a.g_rec && !a.g_occ && !a.dfm && a.dx && a.dx_bf16;
+  if constexpr (EPL == 8) mfast = v_lane && !BAG && !a.g_rec && !a.g_occ && !a.dfm && a.dx && a.dx_bf16;
   for (int m = wid; m < nmd; m += 4) {  // medium rows: one per wave (wave-uniform)
     const int k = rowl[kBkSlots - 1 - m];
     const int ms = seg[k], mlen = cur[k] - seg[k];
@@ -1310,7 +1310,7 @@ __global__ __launch_bounds__(256) void bk_apply_kernel(BankArgs bank, LgWs w, Ap
     } else if (live) {
       for (int j = wk; j < mlen; j += WPW) {
         float g[EPL];
-        lookup_grad<EPL>(a, P[ms + j], f, D, e0, v_lane, w_lane, g);
+        lookup_grad<EPL, BAG>(a, P[ms + j], f, D, e0, v_lane, w_lane, g);
 #pragma unroll
         for (int q = 0; q < EPL; ++q) mx = fmaxf(mx, fabsf(g[q]));
       }
@@ -1337,7 +1337,7 @@ __global__ __launch_bounds__(256) void bk_apply_kernel(BankArgs bank, LgWs w, Ap
     } else if (live) {
       for (int j = wk; j < mlen; j += WPW) {
         float g[EPL];
-        lookup_grad<EPL>(a, P[ms + j], f, D, e0, v_lane, w_lane, g);
+        lookup_grad<EPL, BAG>(a, P[ms + j], f, D, e0, v_lane, w_lane, g);
 #pragma unroll
         for (int q = 0; q < EPL; ++q) sa[q] += llrint(ldexp(static_cast<double>(g[q]), S));
       }
@@ -1492,13 +1492,13 @@ static mrec_status lg_apply_args(const mrec_table_bank *bank, const BankArgs &ba
 
 // the chunked kernels and the per-row apply (fused: the bucket kernel first, the
 // per-row apply then walks only the huge segments' slots)
-template <typename T, int L>
+template <typename T, int L, bool BAG = false>
 static void lg_launch_apply(const BankArgs &ba, int64_t batch, const LgWs &w, const ApplyArgs &a,
                             int stride, int fused_nb, int G, int lognb, const CoReduce &co,
                             int co_blocks, hipStream_t s) {
   dim3 gc(kLgApplyBlocks), gu(kLgApplyBlocks);
   if (fused_nb) {
-    bk_apply_kernel<T, L><<<dim3(fused_nb + co_blocks), 256, 0, s>>>(ba, w, a, G, lognb, co);
+    bk_apply_kernel<T, L, BAG><<<dim3(fused_nb + co_blocks), 256, 0, s>>>(ba, w, a, G, lognb, co);
     // only huge segments are left: as many workgroups as their slots (mostly holes)
     const int64_t N = batch * ba.n_tables;
     const int64_t ul = (N + kLgHuge) / (kLgHuge + 1) + 1;
@@ -1520,19 +1520,28 @@ static void lg_launch_apply(const BankArgs &ba, int64_t batch, const LgWs &w, co
       stall = std::atoi(e);
       if (stall) bound = 1 << 14;
     }
-    lg_huge_kernel<T, L><<<dim3(static_cast<unsigned>(std::min<int64_t>(need, 2 * cus))), 256, 0, s>>>(
+    lg_huge_kernel<T, L, BAG><<<dim3(static_cast<unsigned>(std::min<int64_t>(need, 2 * cus))), 256, 0, s>>>(
         ba, batch, w, a, stride, stall, bound);
     return;
   }
-  lg_longmax_kernel<T, L><<<gc, 256, 0, s>>>(ba, batch, w, a);
-  lg_longacc_kernel<T, L><<<gc, 256, 0, s>>>(ba, batch, w, a, stride);
-  lg_apply_kernel<T, L><<<gu, 256, 0, s>>>(ba, batch, w, a, stride);
+  lg_longmax_kernel<T, L, BAG><<<gc, 256, 0, s>>>(ba, batch, w, a);
+  lg_longacc_kernel<T, L, BAG><<<gc, 256, 0, s>>>(ba, batch, w, a, stride);
+  lg_apply_kernel<T, L, BAG><<<gu, 256, 0, s>>>(ba, batch, w, a, stride);
 }
+
+static void lg_dispatch_apply_bag(mrec_dtype dtype, int lpr, const BankArgs &ba, int64_t batch,
+                                  const LgWs &w, const ApplyArgs &a, int stride, int fused_nb,
+                                  int G, int lognb, hipStream_t s, const CoReduce &co,
+                                  int co_blocks);
 
 static void lg_dispatch_apply(mrec_dtype dtype, int lpr, const BankArgs &ba, int64_t batch,
                               const LgWs &w, const ApplyArgs &a, int stride, int fused_nb, int G,
                               int lognb, hipStream_t s, const CoReduce &co = CoReduce{},
                               int co_blocks = 0) {
+  if (a.bag) {  // the bag-indirection instantiations (below: they follow every other kernel)
+    lg_dispatch_apply_bag(dtype, lpr, ba, batch, w, a, stride, fused_nb, G, lognb, s, co, co_blocks);
+    return;
+  }
 #define MREC_LG(T, L) \
   lg_launch_apply<T, L>(ba, batch, w, a, stride, fused_nb, G, lognb, co, co_blocks, s)
   if (dtype == MREC_BF16) {
@@ -1648,6 +1657,36 @@ mrec_status mrec_emb_bwd_large_fused_ex(const mrec_table_bank *bank, const mrec_
                        stream);
 }
 
+mrec_status mrec_emb_bwd_large_fused_bag(const mrec_table_bank *bank, const mrec_ids *ids,
+                                         int64_t batch, void *workspace, size_t ws_bytes,
+                                         int32_t *d_oob_flag, const void *dx, mrec_dtype dx_dtype,
+                                         int64_t dx_ld, const float *dfm, const float *fm_sum,
+                                         const void *x0, mrec_dtype x0_dtype, int64_t x0_ld,
+                                         const float *dw, mrec_bwd_mode mode, float lr,
+                                         uint64_t seed, const uint64_t *d_step, void *grad,
+                                         int32_t n_reduce, const mrec_gemm_call *reduce,
+                                         mrec_stream stream, int32_t bag_len,
+                                         const float *bag_scale) {
+  MREC_CHECK_ARG(bank != nullptr, "NULL bank");
+  MREC_CHECK_ARG(bag_len >= 1, "bag_len < 1");
+  MREC_CHECK_ARG(batch >= 0 && batch % bag_len == 0, "batch is not a multiple of bag_len");
+  MREC_CHECK_ARG(bag_scale != nullptr, "bag_scale is NULL");
+  MREC_CHECK_ARG(dfm == nullptr, "the FM term is undefined for bags (dfm must be NULL)");
+  BankArgs ba;
+  int es = 0, lpr = 0;
+  mrec_status st = make_bank_args(bank, &ba, &es, &lpr);
+  if (st != MREC_OK) return st;
+  ApplyArgs a{};
+  st = lg_apply_args(bank, ba, dx, dx_dtype, dx_ld, dfm, fm_sum, x0, x0_dtype, x0_ld, dw, mode,
+                     lr, seed, d_step, grad, &a);
+  if (st != MREC_OK) return st;
+  a.bag = bag_len;  // (dx / dw hold batch / bag_len rows: one per bag)
+  a.bag_scale = bag_scale;
+  a.g_F = ba.n_tables;
+  return lg_fused_impl(bank, ids, batch, workspace, ws_bytes, d_oob_flag, a, n_reduce, reduce,
+                       stream);
+}
+
 mrec_status mrec_emb_bwd_large_fused_given(const mrec_table_bank *bank, const mrec_ids *ids,
                                            int64_t batch, void *workspace, size_t ws_bytes,
                                            int32_t *d_oob_flag, const mrec_given_grads *given,
@@ -1708,3 +1747,31 @@ mrec_status mrec_emb_bwd_large_fused(const mrec_table_bank *bank, const mrec_ids
 }
 
 }  // extern "C"
+
+// mrec_emb_bwd_large_fused_bag's kernels.  Dispatched last in the file, so the code
+// object lays the other kernels out as it would without them.
+static void lg_dispatch_apply_bag(mrec_dtype dtype, int lpr, const BankArgs &ba, int64_t batch,
+                                  const LgWs &w, const ApplyArgs &a, int stride, int fused_nb,
+                                  int G, int lognb, hipStream_t s, const CoReduce &co,
+                                  int co_blocks) {
+#define MREC_LGB(T, L) \
+  lg_launch_apply<T, L, true>(ba, batch, w, a, stride, fused_nb, G, lognb, co, co_blocks, s)
+  if (dtype == MREC_BF16) {
+    switch (lpr) {
+      case 1: MREC_LGB(uint16_t, 1); break;
+      case 2: MREC_LGB(uint16_t, 2); break;
+      case 4: MREC_LGB(uint16_t, 4); break;
+      case 8: MREC_LGB(uint16_t, 8); break;
+      default: MREC_LGB(uint16_t, 16); break;
+    }
+  } else {
+    switch (lpr) {
+      case 1: MREC_LGB(float, 1); break;
+      case 2: MREC_LGB(float, 2); break;
+      case 4: MREC_LGB(float, 4); break;
+      case 8: MREC_LGB(float, 8); break;
+      default: MREC_LGB(float, 16); break;
+    }
+  }
+#undef MREC_LGB
+}

@@ -298,6 +298,12 @@ def _plan(bank: EmbeddingBank, ids, start: int, count: int, flag):
     ws_bytes = _mrec.lib().mrec_emb_bwd_workspace_size(n, count)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=bank.weight.device)
     idd = _ids_desc(ids, start, count) if (start or count != ids[0].shape[0]) else _ids_desc(ids)
+    if idd.struct.pad_negative and count > _mrec.BWD_HASH_MAX_BATCH and flag is None:
+        # a padded view of more than BWD_HASH_MAX_BATCH entries would be planned in the
+        # hash layout, which the plain apply does not read (mrec.h, the layout rule above
+        # mrec_emb_bwd_plan): plan it as plain ids -- the sorted plan skips a negative id
+        # just the same, and without a flag nothing else tells the two apart
+        idd = _mrec.IdsDesc(idd.tensors, pad_negative=False)
     _mrec.call("mrec_emb_bwd_plan", bank.desc().ref(), idd.ref(), count, ws.data_ptr(), ws_bytes,
                _mrec.ptr(flag), bank.step_counter().data_ptr(), _mrec.stream_handle())
     return ws, ws_bytes
@@ -350,9 +356,10 @@ def _make_plan(bank: EmbeddingBank, ids, batch: int):
 
 
 def _apply(bank: EmbeddingBank, ws, ws_bytes, count, dx=None, dfm=None, fm_sum=None, x0=None,
-           dw=None, grad=None):
+           dw=None, grad=None, bag=None):
     """Run the fused backward for lookups [0, count) described by ``ws``; the
-    per-sample tensors must already be sliced to the same chunk."""
+    per-sample tensors must already be sliced to the same chunk.  ``bag`` = (L, scale):
+    the lookups are the positions of count / L pooled bags (mrec_emb_bwd_apply_bag)."""
     mode, lr = bank.apply_mode()
     dx_dt = _mrec.dtype_code(dx.dtype) if dx is not None else _mrec.F32
     x0_dt = _mrec.dtype_code(x0.dtype) if x0 is not None else _mrec.F32
@@ -360,12 +367,16 @@ def _apply(bank: EmbeddingBank, ws, ws_bytes, count, dx=None, dfm=None, fm_sum=N
     from pytorchrec_amd import dense as dense_ops
     jobs = dense_ops.take_pending(dense_ops.CO_REDUCE_MAX)
     arr = (_mrec.GemmCall * len(jobs))(*[j.struct() for j in jobs]) if jobs else None
-    _mrec.call("mrec_emb_bwd_apply_ex", bank.desc().ref(), count, ws.data_ptr(), ws_bytes,
-               _mrec.ptr(dx), dx_dt, dx.stride(0) if dx is not None else 0,
-               _mrec.ptr(dfm), _mrec.ptr(fm_sum), _mrec.ptr(x0), x0_dt,
-               x0.stride(0) if x0 is not None else 0, _mrec.ptr(dw), mode, float(lr),
-               bank.next_seed(), bank.step_counter().data_ptr(), _mrec.ptr(grad), len(jobs),
-               arr, _mrec.stream_handle())
+    args = (bank.desc().ref(), count, ws.data_ptr(), ws_bytes,
+            _mrec.ptr(dx), dx_dt, dx.stride(0) if dx is not None else 0,
+            _mrec.ptr(dfm), _mrec.ptr(fm_sum), _mrec.ptr(x0), x0_dt,
+            x0.stride(0) if x0 is not None else 0, _mrec.ptr(dw), mode, float(lr),
+            bank.next_seed(), bank.step_counter().data_ptr(), _mrec.ptr(grad), len(jobs),
+            arr, _mrec.stream_handle())
+    if bag is None:
+        _mrec.call("mrec_emb_bwd_apply_ex", *args)
+    else:
+        _mrec.call("mrec_emb_bwd_apply_bag", *args, int(bag[0]), bag[1].data_ptr())
     del jobs
 
 
@@ -393,14 +404,14 @@ def _large_ws(bank: EmbeddingBank, batch: int) -> torch.Tensor:
 
 
 def _backward_large(bank: EmbeddingBank, ids, batch, grad, dx=None, dfm=None, fm_sum=None,
-                    x0=None, dw=None):
+                    x0=None, dw=None, bag=None):
     """One device-wide plan + ONE update per row for batches beyond a plan
     workgroup (DIN's B x L history lookups): emb_bwd_large.hip, one call
     (mrec_emb_bwd_large_fused: the bucketed plan with the updates in the bucket
     kernel; the plan / apply pair when the batch is too large for it)."""
     ws = _large_ws(bank, batch)
     mode, lr = bank.apply_mode()
-    if not LARGE_FUSED:
+    if not LARGE_FUSED and bag is None:
         _mrec.call("mrec_emb_bwd_large_plan", bank.desc().ref(), _ids_desc(ids).ref(), batch,
                    ws.data_ptr(), ws.numel(), None, _mrec.stream_handle())
         _mrec.call("mrec_emb_bwd_large_apply", bank.desc().ref(), batch, ws.data_ptr(),
@@ -411,8 +422,13 @@ def _backward_large(bank: EmbeddingBank, ids, batch, grad, dx=None, dfm=None, fm
     jobs = dense_ops.take_pending(dense_ops.CO_REDUCE_MAX)
     arr = (_mrec.GemmCall * len(jobs))(*[j.struct() for j in jobs]) if jobs else None
     args = _large_apply_args(bank, grad, dx, dfm, fm_sum, x0, dw, mode, lr)
-    _mrec.call("mrec_emb_bwd_large_fused_ex", bank.desc().ref(), _ids_desc(ids).ref(), batch,
-               ws.data_ptr(), ws.numel(), None, *args[:-1], len(jobs), arr, args[-1])
+    if bag is None:
+        _mrec.call("mrec_emb_bwd_large_fused_ex", bank.desc().ref(), _ids_desc(ids).ref(), batch,
+                   ws.data_ptr(), ws.numel(), None, *args[:-1], len(jobs), arr, args[-1])
+    else:  # the lookups are the positions of batch / L pooled bags
+        _mrec.call("mrec_emb_bwd_large_fused_bag", bank.desc().ref(), _ids_desc(ids).ref(), batch,
+                   ws.data_ptr(), ws.numel(), None, *args[:-1], len(jobs), arr, args[-1],
+                   int(bag[0]), bag[1].data_ptr())
     del jobs
     if bank.check_ids and not torch.cuda.is_current_stream_capturing():
         bank.check_flags()
@@ -429,22 +445,37 @@ def _large_apply_args(bank, grad, dx, dfm, fm_sum, x0, dw, mode, lr):
 
 
 def _backward_into_bank(bank: EmbeddingBank, ids, batch, plan_ws, dx=None, dfm=None,
-                        fm_sum=None, x0=None, dw=None):
-    """Shared backward: returns the dense grad (dense mode) or None (fused SGD)."""
+                        fm_sum=None, x0=None, dw=None, bag=None):
+    """Shared backward: returns the dense grad (dense mode) or None (fused SGD).
+    ``bag`` = (L, scale [B, F]): ``ids`` are the padded lookup ids of a pooled gather,
+    ``batch`` = B * L, and dx / dw hold one row per bag."""
     grad = None
     if bank.update == "dense":
         grad = torch.zeros_like(bank.weight)
     if plan_ws is not None:
         ws, wsb = plan_ws.get() if isinstance(plan_ws, _AsyncPlan) else plan_ws
-        _apply(bank, ws, wsb, batch, dx, dfm, fm_sum, x0, dw, grad)
+        _apply(bank, ws, wsb, batch, dx, dfm, fm_sum, x0, dw, grad, bag)
         return grad
     if batch > _mrec.BWD_MAX_BATCH and bank.total_rows <= LARGE_MAX_ROWS:
-        _backward_large(bank, ids, batch, grad, dx, dfm, fm_sum, x0, dw)
+        _backward_large(bank, ids, batch, grad, dx, dfm, fm_sum, x0, dw, bag)
         return grad
     if bank.update == "adam" and batch > _mrec.BWD_MAX_BATCH:
         raise NotImplementedError("fused Adam takes one apply per step: batches above "
                                   f"{_mrec.BWD_MAX_BATCH} lookups per table need the large-batch "
                                   "path (banks up to 2^24 rows)")
+    if bag is not None:
+        # bag-aligned chunks: whole bags per plan / apply pair, dx / dw / scale by bags
+        L, scale = bag
+        if L > _mrec.BWD_MAX_BATCH:
+            raise ValueError(f"a bag of {L} ids exceeds the {_mrec.BWD_MAX_BATCH} lookups of one "
+                             "plan / apply call")
+        step = (_mrec.BWD_MAX_BATCH // L) * L
+        for s in range(0, batch, step):
+            c = min(step, batch - s)
+            ws, wsb = _plan(bank, ids, s, c, None)
+            sb = (lambda t: None if t is None else t[s // L:(s + c) // L])
+            _apply(bank, ws, wsb, c, sb(dx), None, None, None, sb(dw), grad, (L, sb(scale)))
+        return grad
     for s, c in _chunks(batch):
         if c == 0:
             continue
@@ -528,6 +559,103 @@ def gather(bank: EmbeddingBank, ids: Sequence[torch.Tensor], out_dtype=None, wit
     # will run, so the plan can be queued ahead of it)
     return _GatherFn.apply(bank.weight, trigger, bank, ids, out_dtype, with_w,
                            _needs_backward(bank), din_src)
+
+
+# ----------------------------------------------------------------------------
+# autograd: pooled multi-valued lookup  (a bag of ids per field and sample)
+# ----------------------------------------------------------------------------
+
+_POOL_MODES = {"sum": _mrec.POOL_SUM, "mean": _mrec.POOL_MEAN, "sqrtn": _mrec.POOL_SQRTN}
+_POOL_PADS = {"zero": _mrec.POOL_PAD_ZERO, "negative": _mrec.POOL_PAD_NEGATIVE}
+
+
+class _PoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, weight, trigger, bank: EmbeddingBank, ids: List[torch.Tensor], mode: int,
+                pad: int, out_dtype, want_w: bool, need_bwd: bool):
+        B, L = ids[0].shape
+        F, D = bank.n_tables, bank.dim
+        dev = weight.device
+        out = torch.empty(B, F * D, dtype=out_dtype, device=dev)
+        w_out = torch.empty(B, F, dtype=torch.float32, device=dev) if want_w else None
+        scale = torch.empty(B, F, dtype=torch.float32, device=dev)
+        # the padded lookup ids the backward plans from, built by the gather launch
+        lookup = torch.empty(F, B * L, dtype=torch.int32, device=dev) if need_bwd else None
+        flag = _oob_flag(bank, dev)
+        if B:
+            _mrec.call("mrec_emb_pool_fwd", bank.desc().ref(), _mrec.IdsDesc.bags(ids).ref(), B, L,
+                       mode, pad, out.data_ptr(), _mrec.dtype_code(out_dtype), out.stride(0),
+                       _mrec.ptr(w_out), scale.data_ptr(), _mrec.ptr(lookup), _mrec.ptr(flag),
+                       _mrec.stream_handle())
+        lids = PaddedIds([lookup[f] for f in range(F)]) if need_bwd else None
+        plan_ws = None
+        if need_bwd and 0 < B * L <= _mrec.BWD_MAX_BATCH:
+            plan_ws = _make_plan(bank, lids, B * L)
+        _raise_if_oob(flag)
+        ctx.bank, ctx.ids, ctx.B, ctx.L, ctx.plan_ws, ctx.scale = bank, lids, B, L, plan_ws, scale
+        if want_w:
+            return out, w_out
+        return out
+
+    @staticmethod
+    def backward(ctx, dout, dw_out=None):
+        bank = ctx.bank
+        dx = dout.contiguous() if dout is not None else None
+        dw = None
+        if dw_out is not None:
+            if bank.n_tables != 1:
+                raise NotImplementedError("first-order grads through pooled_gather need one "
+                                          "table per call")
+            dw = dw_out.reshape(-1).contiguous().float()
+        grad = None
+        if ctx.B:
+            grad = _backward_into_bank(bank, ctx.ids, ctx.B * ctx.L, ctx.plan_ws, dx=dx, dw=dw,
+                                       bag=(ctx.L, ctx.scale))
+        elif bank.update == "dense":
+            grad = torch.zeros_like(bank.weight)
+        return grad, None, None, None, None, None, None, None, None
+
+
+def pooled_gather(bank: EmbeddingBank, ids: Sequence[torch.Tensor], mode: str = "sum",
+                  pad: str = "zero", out_dtype=None, with_w: bool = False):
+    """out[b, f*D:(f+1)*D] = s * sum over the valid ids of bag ids[f][b, :] of their
+    rows of table f, s = 1 ("sum"), 1/n ("mean") or 1/sqrt(n) ("sqrtn", the reference's
+    SVD++ history term, SVDPP.py:49-55), n = the bag's valid count.
+
+    ``ids``: F tensors [B, L] (int32 or int64; one L per call).  ``pad`` = "zero": id 0
+    is padding and a negative id is out of range; "negative": a negative id is padding
+    and id 0 a real row.  An empty bag gives a zero row (the reference: NaN) and no
+    gradient.  Returns [B, F*D] (and the pooled first-order weights [B, F] if
+    ``with_w``).  Works under every update mode of the bank.
+    """
+    ids = list(ids)
+    if len(ids) != bank.n_tables:
+        raise ValueError(f"expected {bank.n_tables} id tensors, got {len(ids)}")
+    if mode not in _POOL_MODES:
+        raise ValueError(f"mode must be one of {sorted(_POOL_MODES)}, got {mode!r}")
+    if pad not in _POOL_PADS:
+        raise ValueError(f"pad must be one of {sorted(_POOL_PADS)}, got {pad!r}")
+    if any(t.dim() != 2 or t.shape != ids[0].shape or t.dtype != ids[0].dtype for t in ids):
+        raise ValueError("pooled_gather takes [B, L] id tensors of one shape and dtype")
+    if ids[0].dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"ids must be int32 or int64, got {ids[0].dtype}")
+    if ids[0].shape[1] < 1:
+        raise ValueError("bags must hold at least one position (L >= 1)")
+    if with_w and not bank.has_w:
+        raise ValueError("with_w needs a bank built with_first_order=True")
+    from pytorchrec_amd.sharding import ShardedEmbeddingBank
+    if isinstance(bank, ShardedEmbeddingBank):
+        raise NotImplementedError("pooled_gather does not take a row-sharded bank")
+    out_dtype = out_dtype or bank.weight.dtype
+    if not bank.weight.is_cuda:
+        return cpu_path.pooled_gather(bank, ids, mode, pad, out_dtype, with_w)
+    # read in place when every field is contiguous along the bag with one row stride
+    L = ids[0].shape[1]
+    st = ids[0].stride(0)
+    if any(t.stride(1) != 1 or t.stride(0) != st or st < L for t in ids):
+        ids = [t.contiguous() for t in ids]
+    return _PoolFn.apply(bank.weight, _trigger(bank), bank, ids, _POOL_MODES[mode],
+                         _POOL_PADS[pad], out_dtype, with_w, _needs_backward(bank))
 
 
 _TRIGGERS = {}
@@ -712,5 +840,6 @@ def rows_to_bytes(bank: EmbeddingBank) -> int:
     return bank.weight.numel() * bank.weight.element_size()
 
 
-__all__ = ["EmbeddingBank", "gather", "interact", "fm2_dense", "init_bank_", "rows_to_bytes"]
+__all__ = ["EmbeddingBank", "gather", "pooled_gather", "interact", "fm2_dense", "init_bank_",
+           "rows_to_bytes"]
 

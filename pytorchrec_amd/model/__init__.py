@@ -4,4 +4,5 @@ from pytorchrec_amd.model.DeepFM import FM, DeepFM
 from pytorchrec_amd.model.DCNv2 import DCNv2
 from pytorchrec_amd.model.DIN import DIN
 from pytorchrec_amd.model.FunkSVD import FunkSVD
+from pytorchrec_amd.model.SVDPP import SVDPP
 from pytorchrec_amd.model.models import get_model_type, model_name_list
