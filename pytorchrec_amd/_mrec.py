@@ -221,6 +221,18 @@ _ids_p = ctypes.POINTER(Ids)
 _op_p = ctypes.POINTER(Operand)
 _epi_p = ctypes.POINTER(Epilogue)
 
+# the parts every embedding-backward signature is composed of (mrec.h order; the stream
+# follows, then what a later ABI appended)
+_WS = [_bank_p, _i64, _vp, ctypes.c_size_t]             # bank, batch, workspace, ws_bytes
+_LG_WS = [_bank_p, _ids_p, _i64, _vp, ctypes.c_size_t, _vp]  # bank, ids, ..., d_oob_flag
+_GRAD_SRC = [_vp, ctypes.c_int, _i64, _vp, _vp, _vp, ctypes.c_int, _i64, _vp]  # grad_source()
+_GIVEN = [_vp, _i64, _i64, _i64]                        # g_occ, g_ld, chunk, chunk_stride
+# wire, rec_bytes, wire_dtype, pref, cap_rows, chunk, chunk_stride
+_WIRE = [_vp, _i32, _i32, _vp, _i32, _i64, _i64]
+_UPDATE = [ctypes.c_int, _f32, ctypes.c_uint64, _vp, _vp]    # mode, lr, seed, d_step, grad
+_CO = [_i32, ctypes.POINTER(GemmCall)]                  # n_reduce, reduce
+_BAG = [_i32, _vp]                                      # bag_len, bag_scale
+
 # name -> (restype, argtypes); the set the header declares (checked by tests)
 SIGNATURES = {
     "mrec_abi_version": (ctypes.c_int, []),
@@ -259,40 +271,19 @@ SIGNATURES = {
     "mrec_emb_bwd_workspace_size": (ctypes.c_size_t, [_i32, _i64]),
     "mrec_emb_bwd_plan": (ctypes.c_int, [_bank_p, _ids_p, _i64, _vp, ctypes.c_size_t, _vp, _vp,
                                          _vp]),
-    "mrec_emb_bwd_apply": (ctypes.c_int, [_bank_p, _i64, _vp, ctypes.c_size_t, _vp, ctypes.c_int,
-                                          _i64, _vp, _vp, _vp, ctypes.c_int, _i64, _vp,
-                                          ctypes.c_int, _f32, ctypes.c_uint64, _vp, _vp, _vp]),
-    "mrec_emb_bwd_apply_ex": (ctypes.c_int, [_bank_p, _i64, _vp, ctypes.c_size_t, _vp, ctypes.c_int,
-                                             _i64, _vp, _vp, _vp, ctypes.c_int, _i64, _vp,
-                                             ctypes.c_int, _f32, ctypes.c_uint64, _vp, _vp, _i32,
-                                             ctypes.POINTER(GemmCall), _vp]),
-    "mrec_emb_bwd_apply_bag": (ctypes.c_int, [_bank_p, _i64, _vp, ctypes.c_size_t, _vp, ctypes.c_int,
-                                              _i64, _vp, _vp, _vp, ctypes.c_int, _i64, _vp,
-                                              ctypes.c_int, _f32, ctypes.c_uint64, _vp, _vp, _i32,
-                                              ctypes.POINTER(GemmCall), _vp, _i32, _vp]),
-    "mrec_emb_bwd_apply_given": (ctypes.c_int, [_bank_p, _i64, _vp, ctypes.c_size_t, _vp,
-                                                ctypes.c_int, _i64, _vp, _vp, _vp, ctypes.c_int,
-                                                _i64, _vp, _vp, _i64, _i64, _i64, ctypes.c_int,
-                                                _f32, ctypes.c_uint64, _vp, _vp, _i32,
-                                                ctypes.POINTER(GemmCall), _vp]),
-    "mrec_emb_bwd_apply_rec": (ctypes.c_int, [_bank_p, _i64, _vp, ctypes.c_size_t, _vp,
-                                              ctypes.c_int, _i64, _vp, _vp, _vp, ctypes.c_int,
-                                              _i64, _vp, ctypes.POINTER(GradRecords), _i32,
-                                              ctypes.POINTER(GemmCall), _vp]),
-    "mrec_emb_bwd_apply_wire": (ctypes.c_int, [_bank_p, _i64, _vp, ctypes.c_size_t, _vp, _i32, _i32,
-                                               _vp, _i32, _i64, _i64, ctypes.c_int, _f32,
-                                               ctypes.c_uint64, _vp, _vp, _i32,
-                                               ctypes.POINTER(GemmCall), _vp]),
-    "mrec_emb_bwd_apply_wire_sgd": (ctypes.c_int, [_bank_p, _i64, _vp, ctypes.c_size_t, _vp, _i32,
-                                                   _i32, _vp, _i32, _i64, _i64, ctypes.c_int, _f32,
-                                                   ctypes.c_uint64, _vp, _vp, _i32,
-                                                   ctypes.POINTER(GemmCall), _vp, _i32, _vp]),
+    "mrec_emb_bwd_apply": (ctypes.c_int, _WS + _GRAD_SRC + _UPDATE + [_vp]),
+    "mrec_emb_bwd_apply_ex": (ctypes.c_int, _WS + _GRAD_SRC + _UPDATE + _CO + [_vp]),
+    "mrec_emb_bwd_apply_bag": (ctypes.c_int, _WS + _GRAD_SRC + _UPDATE + _CO + [_vp] + _BAG),
+    "mrec_emb_bwd_apply_given": (ctypes.c_int, _WS + _GRAD_SRC + _GIVEN + _UPDATE + _CO + [_vp]),
+    "mrec_emb_bwd_apply_rec": (ctypes.c_int, _WS + _GRAD_SRC + [ctypes.POINTER(GradRecords)] + _CO
+                               + [_vp]),
+    "mrec_emb_bwd_apply_wire": (ctypes.c_int, _WS + _WIRE + _UPDATE + _CO + [_vp]),
+    "mrec_emb_bwd_apply_wire_sgd": (ctypes.c_int, _WS + _WIRE + _UPDATE + _CO + [_vp, _i32, _vp]),
     "mrec_shard_bucketize": (ctypes.c_int, [_ids_p, _i32, ctypes.POINTER(ctypes.c_int64), _i64,
                                             _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mrec_shard_gather": (ctypes.c_int, [_bank_p, _vp, _i32, _i32, _vp, _vp]),
-    "mrec_shard_lookup_grad": (ctypes.c_int, [_i64, _i32, _i32, _i32, _vp, _vp, ctypes.c_int,
-                                              _i64, _vp, _vp, _vp, ctypes.c_int, _i64, _vp, _vp,
-                                              _i64, _vp]),
+    "mrec_shard_lookup_grad": (ctypes.c_int, [_i64, _i32, _i32, _i32, _vp] + _GRAD_SRC
+                               + [_vp, _i64, _vp]),
     "mrec_gemm_workspace_size": (ctypes.c_size_t, [_i64, _i64, _i64, _i32]),
     "mrec_gemm": (ctypes.c_int, [_i64, _i64, _i64, _op_p, _op_p, _i64, _i64, _epi_p,
                                  _vp, ctypes.c_int, _i64, _i32, _vp, ctypes.c_size_t, _vp]),
@@ -322,28 +313,13 @@ SIGNATURES = {
     "mrec_kernel_clock_used": (_i32, []),
     "mrec_emb_bwd_large_plan": (ctypes.c_int, [_bank_p, _ids_p, _i64, _vp, ctypes.c_size_t, _vp,
                                                _vp]),
-    "mrec_emb_bwd_large_apply": (ctypes.c_int, [_bank_p, _i64, _vp, ctypes.c_size_t, _vp,
-                                                ctypes.c_int, _i64, _vp, _vp, _vp, ctypes.c_int,
-                                                _i64, _vp, ctypes.c_int, _f32, ctypes.c_uint64,
-                                                _vp, _vp, _vp]),
-    "mrec_emb_bwd_large_fused": (ctypes.c_int, [_bank_p, _ids_p, _i64, _vp, ctypes.c_size_t, _vp,
-                                                _vp, ctypes.c_int, _i64, _vp, _vp, _vp,
-                                                ctypes.c_int, _i64, _vp, ctypes.c_int, _f32,
-                                                ctypes.c_uint64, _vp, _vp, _vp]),
-    "mrec_emb_bwd_large_fused_given": (ctypes.c_int, [_bank_p, _ids_p, _i64, _vp, ctypes.c_size_t,
-                                                      _vp, ctypes.POINTER(GivenGrads), ctypes.c_int,
-                                                      _f32, ctypes.c_uint64, _vp, _vp, _i32,
-                                                      ctypes.POINTER(GemmCall), _vp]),
-    "mrec_emb_bwd_large_fused_ex": (ctypes.c_int, [_bank_p, _ids_p, _i64, _vp, ctypes.c_size_t,
-                                                   _vp, _vp, ctypes.c_int, _i64, _vp, _vp, _vp,
-                                                   ctypes.c_int, _i64, _vp, ctypes.c_int, _f32,
-                                                   ctypes.c_uint64, _vp, _vp, _i32,
-                                                   ctypes.POINTER(GemmCall), _vp]),
-    "mrec_emb_bwd_large_fused_bag": (ctypes.c_int, [_bank_p, _ids_p, _i64, _vp, ctypes.c_size_t,
-                                                    _vp, _vp, ctypes.c_int, _i64, _vp, _vp, _vp,
-                                                    ctypes.c_int, _i64, _vp, ctypes.c_int, _f32,
-                                                    ctypes.c_uint64, _vp, _vp, _i32,
-                                                    ctypes.POINTER(GemmCall), _vp, _i32, _vp]),
+    "mrec_emb_bwd_large_apply": (ctypes.c_int, _WS + _GRAD_SRC + _UPDATE + [_vp]),
+    "mrec_emb_bwd_large_fused": (ctypes.c_int, _LG_WS + _GRAD_SRC + _UPDATE + [_vp]),
+    "mrec_emb_bwd_large_fused_given": (ctypes.c_int, _LG_WS + [ctypes.POINTER(GivenGrads)] + _UPDATE
+                                       + _CO + [_vp]),
+    "mrec_emb_bwd_large_fused_ex": (ctypes.c_int, _LG_WS + _GRAD_SRC + _UPDATE + _CO + [_vp]),
+    "mrec_emb_bwd_large_fused_bag": (ctypes.c_int, _LG_WS + _GRAD_SRC + _UPDATE + _CO + [_vp]
+                                     + _BAG),
     "mrec_head_fwd": (ctypes.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mrec_head_bwd": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp]),
     "mrec_bce_fwd": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp]),
@@ -473,6 +449,16 @@ def dtype_code(t: torch.dtype) -> int:
 
 def ptr(t) -> int | None:
     return None if t is None else t.data_ptr()
+
+
+def grad_source(dx, dfm, fm_sum, x0, dw):
+    """The nine gradient-source arguments of the embedding-backward entry points and of
+    mrec_shard_lookup_grad, from tensors or None: dx pointer, dtype, row stride; dfm;
+    fm_sum; x0 pointer, dtype, row stride; dw."""
+    return (ptr(dx), dtype_code(dx.dtype) if dx is not None else F32,
+            dx.stride(0) if dx is not None else 0, ptr(dfm), ptr(fm_sum),
+            ptr(x0), dtype_code(x0.dtype) if x0 is not None else F32,
+            x0.stride(0) if x0 is not None else 0, ptr(dw))
 
 
 class BankDesc:

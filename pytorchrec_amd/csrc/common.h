@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <type_traits>
 
 #include "mrec.h"
 
@@ -128,6 +129,27 @@ mrec_status make_bank_args(const mrec_table_bank *bank, BankArgs *out, int *elem
 mrec_status make_ids_args(const mrec_ids *ids, int n_tables, IdsArgs *out);
 // the fused optimizer of a mode >= MREC_BWD_ADAGRAD from bank->optim (checked)
 mrec_status make_opt_args(const mrec_table_bank *bank, int mode, OptArgs *out);
+
+// Row geometry dispatch of the embedding-backward kernels: calls
+// f(T{}, std::integral_constant<int, LPR>{}) with the bank's element type (uint16_t
+// for bf16, float) and its lanes per row (row bytes / 16: 1, 2, 4, 8 or 16).
+template <typename T, typename Fn>
+inline void for_lanes_per_row(int lpr, Fn &&f) {
+  switch (lpr) {
+    case 1: f(T{}, std::integral_constant<int, 1>{}); break;
+    case 2: f(T{}, std::integral_constant<int, 2>{}); break;
+    case 4: f(T{}, std::integral_constant<int, 4>{}); break;
+    case 8: f(T{}, std::integral_constant<int, 8>{}); break;
+    default: f(T{}, std::integral_constant<int, 16>{}); break;
+  }
+}
+template <typename Fn>
+inline void for_row_geometry(mrec_dtype dtype, int lpr, Fn &&f) {
+  if (dtype == MREC_BF16)
+    for_lanes_per_row<uint16_t>(lpr, f);
+  else
+    for_lanes_per_row<float>(lpr, f);
+}
 
 // ---------------------------------------------------------------------------
 // device helpers

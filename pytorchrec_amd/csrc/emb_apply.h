@@ -58,6 +58,158 @@ struct ApplyArgs {
   const float *bag_scale;
 };
 
+// One embedding-backward apply as its entry point describes it (host only).  Every
+// extern "C" entry fills the members it has, by name, and hands the request on; a new
+// gradient source or rider is a member here, not another positional list.
+struct BwdRequest {
+  const char *who = "";  // the entry point's own name (error text, ws_layout_check)
+  // gradients derived per lookup from dx / dfm / dw
+  const void *dx = nullptr;
+  mrec_dtype dx_dtype = MREC_F32;
+  int64_t dx_ld = 0;
+  const float *dfm = nullptr;
+  const float *fm_sum = nullptr;
+  const void *x0 = nullptr;
+  mrec_dtype x0_dtype = MREC_F32;
+  int64_t x0_ld = 0;
+  const float *dw = nullptr;
+  // or given as fp32 rows
+  const float *g_occ = nullptr;
+  int64_t g_ld = 0;
+  // or given as wire records (from_wire: the entry takes them, so `wire` must be set)
+  bool from_wire = false;
+  const void *wire = nullptr;
+  mrec_dtype wire_dtype = MREC_F32;
+  int32_t rec_bytes = 0;
+  const int32_t *pref = nullptr;
+  int32_t cap_rows = 0;
+  // the exchange-view chunking of both given forms
+  int64_t chunk = 0;
+  int64_t chunk_stride = 0;
+  // bag indirection (bag: the entry takes pooled bags, so bag_len / bag_scale must be set)
+  bool bag = false;
+  int32_t bag_len = 0;
+  const float *bag_scale = nullptr;
+  // DENSE_GRAD sums into wire records instead of `grad` (mrec_emb_bwd_apply_rec)
+  const mrec_grad_records *rec_out = nullptr;
+  // the update
+  mrec_bwd_mode mode = MREC_BWD_SGD;
+  float lr = 0.f;
+  uint64_t seed = 0;
+  const uint64_t *d_step = nullptr;
+  void *grad = nullptr;
+  // what rides along in the launch
+  int32_t n_reduce = 0;
+  const mrec_gemm_call *reduce = nullptr;
+  const void *sgd_table = nullptr;
+  int32_t sgd_blocks = 0;
+
+  void set_given(const mrec_given_grads &g) {
+    g_occ = g.g_occ, g_ld = g.g_ld;
+    from_wire = g.wire != nullptr;
+    wire = g.wire, wire_dtype = g.wire_dtype, rec_bytes = g.rec_bytes;
+    pref = g.pref, cap_rows = g.cap_rows;
+    chunk = g.chunk, chunk_stride = g.chunk_stride;
+  }
+};
+
+// MREC_CHECK_ARG with the entry point's own name in the error text
+#define MREC_CHECK_REQ(req, cond, msg)                          \
+  do {                                                          \
+    if (!(cond)) {                                              \
+      ::mrec::set_error(std::string((req).who) + ": " + (msg)); \
+      return MREC_EINVAL;                                       \
+    }                                                           \
+  } while (0)
+
+// The checked ApplyArgs of a request: every check the batched and the large-batch
+// path share, each once.  What only one path requires (its batch bounds, the layout
+// rule, record output and SGD tiles, chunk >= 1 on the large path) stays with it.
+static inline mrec_status make_apply_args(const mrec_table_bank *bank, const BankArgs &ba,
+                                          int64_t batch, const BwdRequest &req, ApplyArgs *out) {
+  const auto aligned = [](const void *p, uintptr_t to) {
+    return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0;
+  };
+  const auto f32_or_bf16 = [](mrec_dtype t) { return t == MREC_F32 || t == MREC_BF16; };
+  const auto row_bytes = [](int64_t ld, mrec_dtype t) { return ld * (t == MREC_F32 ? 4 : 2); };
+  const int F = ba.n_tables, D = ba.dim, row = D + (ba.has_w ? 1 : 0);
+  MREC_CHECK_REQ(req, req.mode >= MREC_BWD_DENSE_GRAD && req.mode <= MREC_BWD_ADAM, "bad mode");
+  MREC_CHECK_REQ(req, req.mode != MREC_BWD_DENSE_GRAD || req.grad || req.rec_out,
+                 "DENSE_GRAD needs grad");
+  ApplyArgs a{};
+  if (mrec_status st = make_opt_args(bank, req.mode, &a.opt); st != MREC_OK) return st;
+  if (req.dx) {
+    MREC_CHECK_REQ(req, f32_or_bf16(req.dx_dtype), "dx dtype must be F32/BF16");
+    MREC_CHECK_REQ(req, req.dx_ld >= static_cast<int64_t>(F) * D, "dx_ld < F*dim");
+    MREC_CHECK_REQ(req, aligned(req.dx, 16) && row_bytes(req.dx_ld, req.dx_dtype) % 16 == 0,
+                   "dx must be 16B aligned with 16B-multiple rows");
+  }
+  if (req.dfm) {
+    MREC_CHECK_REQ(req, req.fm_sum != nullptr && req.x0 != nullptr, "dfm needs fm_sum and x0");
+    MREC_CHECK_REQ(req, f32_or_bf16(req.x0_dtype), "x0 dtype must be F32/BF16");
+    MREC_CHECK_REQ(req, req.x0_ld >= static_cast<int64_t>(F) * D, "x0_ld < F*dim");
+    MREC_CHECK_REQ(req, aligned(req.x0, 16) && row_bytes(req.x0_ld, req.x0_dtype) % 16 == 0 &&
+                       aligned(req.fm_sum, 16),
+                   "x0/fm_sum must be 16B aligned with 16B-multiple rows");
+  }
+  MREC_CHECK_REQ(req, req.dw == nullptr || ba.has_w, "dw given but bank has no w column");
+  if (req.from_wire) {
+    MREC_CHECK_REQ(req, !req.dx && !req.dfm && !req.dw && !req.g_occ,
+                   "wire gradients exclude dx / dfm / dw / g_occ");
+    MREC_CHECK_REQ(req, f32_or_bf16(req.wire_dtype), "wire dtype must be BF16/F32");
+    const int es = req.wire_dtype == MREC_BF16 ? 2 : 4;
+    MREC_CHECK_REQ(req, req.rec_bytes > 0 && req.rec_bytes % es == 0 && req.rec_bytes % 4 == 0,
+                   "bad record bytes");
+    MREC_CHECK_REQ(req, req.wire && req.pref && req.cap_rows >= 1,
+                   "NULL wire / pref, cap_rows < 1");
+    MREC_CHECK_REQ(req, req.rec_bytes / es >= row && aligned(req.wire, 4),
+                   "records: pitch >= dim + has_w elements, 4-B aligned");
+    MREC_CHECK_REQ(req, req.chunk >= 1, "chunk (entries per exchange part) must be >= 1");
+    a.g_rec = req.wire;
+    a.g_rec_bf16 = req.wire_dtype == MREC_BF16;
+    a.g_rec_pitch = req.rec_bytes / es;
+    a.g_pref = req.pref;
+    a.g_cap_rows = req.cap_rows;
+  }
+  if (req.g_occ) {
+    MREC_CHECK_REQ(req, !req.dx && !req.dfm && !req.dw, "g_occ excludes dx / dfm / dw");
+    MREC_CHECK_REQ(req, req.g_ld >= row && req.g_ld % 4 == 0 && aligned(req.g_occ, 16),
+                   "g_occ rows must be 16B aligned, g_ld >= dim + has_w, g_ld % 4 == 0");
+    MREC_CHECK_REQ(req, req.chunk >= 0 && (req.chunk == 0 || req.chunk_stride >= F * req.chunk),
+                   "chunk < 0, or chunk_stride < n_tables * chunk");
+  }
+  if (req.bag) {
+    MREC_CHECK_REQ(req, req.bag_len >= 1, "bag_len < 1");
+    MREC_CHECK_REQ(req, batch >= 0 && batch % req.bag_len == 0, "batch is not a multiple of bag_len");
+    MREC_CHECK_REQ(req, req.bag_scale != nullptr, "bag_scale is NULL");
+    MREC_CHECK_REQ(req, req.dfm == nullptr, "the FM term is undefined for bags (dfm must be NULL)");
+    a.bag = req.bag_len;  // (dx / dw hold batch / bag_len rows: one per bag)
+    a.bag_scale = req.bag_scale;
+  }
+  a.dx = req.dx;
+  a.dx_ld = req.dx_ld;
+  a.dx_bf16 = req.dx_dtype == MREC_BF16;
+  a.dfm = req.dfm;
+  a.fm_sum = req.fm_sum;
+  a.x0 = req.x0;
+  a.x0_ld = req.x0_ld;
+  a.x0_bf16 = req.x0_dtype == MREC_BF16;
+  a.dw = req.dw;
+  a.mode = req.mode;
+  a.lr = req.lr;
+  a.seed = req.seed;
+  a.d_step = req.d_step;
+  a.grad = req.grad;
+  a.g_occ = req.g_occ;
+  a.g_ld = req.g_ld;
+  a.chunk = req.chunk;
+  a.chunk_stride = req.chunk_stride;
+  a.g_F = a.o_F = F;
+  a.o_cap = 1;  // (record output, hash layout only: the batched apply fills o_*)
+  *out = a;
+  return MREC_OK;
+}
+
 // lookup i -> its bag (i < 2^31: the entry points check batch), and the bag's scale
 __device__ __forceinline__ float bag_index(const ApplyArgs &a, int64_t &b, int f) {
   b = static_cast<int64_t>(static_cast<uint32_t>(b) / static_cast<uint32_t>(a.bag));

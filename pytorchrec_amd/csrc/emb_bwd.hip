@@ -751,25 +751,9 @@ mrec_status mrec_emb_optim_flush(const mrec_table_bank *bank, mrec_bwd_mode mode
   const int64_t want = (total + wpb - 1) / wpb;
   const dim3 grid(static_cast<unsigned>(std::min<int64_t>(want, 8192)));
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define MREC_FK(T, L) optim_flush_kernel<T, L><<<grid, 256, 0, s>>>(ba, total, a)
-  if (bank->dtype == MREC_BF16) {
-    switch (lpr) {
-      case 1: MREC_FK(uint16_t, 1); break;
-      case 2: MREC_FK(uint16_t, 2); break;
-      case 4: MREC_FK(uint16_t, 4); break;
-      case 8: MREC_FK(uint16_t, 8); break;
-      default: MREC_FK(uint16_t, 16); break;
-    }
-  } else {
-    switch (lpr) {
-      case 1: MREC_FK(float, 1); break;
-      case 2: MREC_FK(float, 2); break;
-      case 4: MREC_FK(float, 4); break;
-      case 8: MREC_FK(float, 8); break;
-      default: MREC_FK(float, 16); break;
-    }
-  }
-#undef MREC_FK
+  for_row_geometry(bank->dtype, lpr, [&](auto t, auto l) {
+    optim_flush_kernel<decltype(t), decltype(l)::value><<<grid, 256, 0, s>>>(ba, total, a);
+  });
   return launch_status("mrec_emb_optim_flush");
 }
 
@@ -850,36 +834,136 @@ mrec_status mrec_diag_plan_hash_variant(const mrec_table_bank *bank, const mrec_
 
 }  // extern "C"
 
-struct GivenWire {  // mrec_emb_bwd_apply_wire: given gradients as wire records
-  const void *wire;
-  int bf16;
-  int pitch;  // elements per record
-  const int32_t *pref;
-  int64_t cap_rows;
-};
-struct BagGrad {  // mrec_emb_bwd_apply_bag: the lookups are the positions of pooled bags
-  int32_t bag_len;
-  const float *scale;
-};
-struct RecOut {  // mrec_emb_bwd_apply_rec: DENSE_GRAD sums into wire records
-  void *wire;
-  int rec_dw;
-  const int32_t *pref;
-  int cap;
-  int64_t cap_rows;
+// one apply launch: what every instantiation of the two apply kernels is given
+struct ApplyLaunch {
+  BankArgs ba;
+  int64_t batch;
+  const void *ws;
+  ApplyArgs a;
+  int seg_blocks, sm_blocks, apply_blocks;
+  CoReduce co;
+  KClock kc;
+  dim3 grid;
+  hipStream_t s;
 };
 
-static mrec_status apply_impl(const mrec_table_bank *bank, int64_t batch, const void *workspace,
-                              size_t ws_bytes, const void *dx, mrec_dtype dx_dtype, int64_t dx_ld,
-                              const float *dfm, const float *fm_sum, const void *x0,
-                              mrec_dtype x0_dtype, int64_t x0_ld, const float *dw,
-                              const float *g_occ, int64_t g_ld, int64_t chunk,
-                              int64_t chunk_stride, mrec_bwd_mode mode, float lr, uint64_t seed,
-                              const uint64_t *d_step, void *grad, int32_t n_reduce,
-                              const mrec_gemm_call *reduce, mrec_stream stream,
-                              const GivenWire *gw = nullptr, const RecOut *ro = nullptr,
-                              const void *sgd_table = nullptr, int32_t sgd_blocks = 0,
-                              const BagGrad *bag = nullptr);
+// hash layout, update mode M fixed at compile time (-1: the fused optimizers, a.mode)
+template <typename T, int L, int M, bool BAG>
+static void launch_hash(const ApplyLaunch &x) {
+  if constexpr (BAG)  // (bags: unclocked)
+    apply_hash_kernel<T, L, M, false, true><<<x.grid, 256, 0, x.s>>>(
+        x.ba, x.batch, x.ws, x.a, x.seg_blocks, x.sm_blocks, x.co, x.kc);
+  else if (x.kc.buf)
+    apply_hash_kernel<T, L, M, true><<<x.grid, 256, 0, x.s>>>(
+        x.ba, x.batch, x.ws, x.a, x.seg_blocks, x.sm_blocks, x.co, x.kc);
+  else
+    apply_hash_kernel<T, L, M, false><<<x.grid, 256, 0, x.s>>>(
+        x.ba, x.batch, x.ws, x.a, x.seg_blocks, x.sm_blocks, x.co, x.kc);
+}
+
+template <typename T, int L, bool BAG>
+static void launch_sorted(const ApplyLaunch &x) {
+  apply_kernel<T, L, BAG><<<x.grid, 256, 0, x.s>>>(x.ba, x.batch, x.ws, x.a, x.seg_blocks,
+                                                  x.apply_blocks, x.co);
+}
+
+// BAG: the bag-indirection instantiations (mrec_emb_bwd_apply_bag only), dispatched
+// after every other kernel of the file, whose layout they leave alone
+template <bool BAG>
+static void launch_apply(mrec_dtype dtype, int lpr, bool hash, const ApplyLaunch &x) {
+  for_row_geometry(dtype, lpr, [&](auto t, auto l) {
+    using T = decltype(t);
+    constexpr int L = decltype(l)::value;
+    if (hash) {
+      switch (x.a.mode) {
+        case MREC_BWD_SGD: launch_hash<T, L, MREC_BWD_SGD, BAG>(x); break;
+        case MREC_BWD_SGD_SR: launch_hash<T, L, MREC_BWD_SGD_SR, BAG>(x); break;
+        case MREC_BWD_DENSE_GRAD: launch_hash<T, L, MREC_BWD_DENSE_GRAD, BAG>(x); break;
+        default: launch_hash<T, L, -1, BAG>(x); break;
+      }
+    } else {
+      launch_sorted<T, L, BAG>(x);
+    }
+  });
+}
+
+// every mrec_emb_bwd_apply* entry point: its leading arguments and its request
+static mrec_status apply_request(const mrec_table_bank *bank, int64_t batch, const void *workspace,
+                                 size_t ws_bytes, mrec_stream stream, const BwdRequest &req) {
+  BankArgs ba;
+  int eb, lpr;
+  mrec_status st = make_bank_args(bank, &ba, &eb, &lpr);
+  if (st != MREC_OK) return st;
+  MREC_CHECK_REQ(req, batch >= 0 && batch <= kMaxPlanKeys,
+                 "batch must be in [0, MREC_BWD_MAX_BATCH]");
+  MREC_CHECK_REQ(req, workspace != nullptr, "workspace is NULL");
+  if (ws_bytes < mrec_emb_bwd_workspace_size(ba.n_tables, batch)) {
+    set_error(std::string(req.who) + ": workspace too small");
+    return MREC_ENOSPC;
+  }
+  // the layout this apply reads (hash: batch <= 4096, or an exchange view's given
+  // gradients up to 8192 entries) must be the one the workspace's plan wrote
+  const bool hash = hash_layout(batch, req.g_occ != nullptr || req.from_wire);
+  if ((st = ws_layout_check(workspace, hash ? kLayoutHash : kLayoutSorted, batch, ba.n_tables,
+                            req.who)) != MREC_OK)
+    return st;
+  ApplyLaunch x{};
+  if ((st = make_apply_args(bank, ba, batch, req, &x.a)) != MREC_OK) return st;
+  const int F = ba.n_tables;
+  // (g_occ may be unchunked on this path, chunk == 0: make_apply_args allows it; a wire
+  // view is chunked like the ids it answers, its part stride covers the tables)
+  MREC_CHECK_REQ(req, !req.from_wire || req.chunk_stride >= F * req.chunk,
+                 "chunk_stride < n_tables * chunk");
+  if (const mrec_grad_records *ro = req.rec_out) {
+    MREC_CHECK_REQ(req, ro->rec_bytes > 0 && ro->rec_bytes % 4 == 0, "bad record bytes");
+    MREC_CHECK_REQ(req, req.mode == MREC_BWD_DENSE_GRAD && req.grad == nullptr,
+                   "records take DENSE_GRAD sums");
+    MREC_CHECK_REQ(req, hash_layout(batch, false),
+                   "record output needs the hash layout (batch <= 4096)");
+    MREC_CHECK_REQ(req, ro->wire && ro->pref && ro->cap >= 1 && ro->cap_rows >= 1 &&
+                       (reinterpret_cast<uintptr_t>(ro->wire) & 3) == 0,
+                   "records: NULL wire / pref, bad cap");
+    MREC_CHECK_REQ(req, ro->rec_bytes >= (ba.dim + (ba.has_w ? 1 : 0)) * eb,
+                   "record narrower than a row");
+    x.a.grad = bank->data;  // (the raw loads of the old sums read the rows: never used)
+    x.a.o_rec = static_cast<uint32_t *>(ro->wire);
+    x.a.o_rec_dw = ro->rec_bytes / 4;
+    x.a.o_pref = ro->pref;
+    x.a.o_cap = ro->cap;
+    x.a.o_cap_rows = ro->cap_rows;
+  }
+  // data-parallel dense SGD tiles: they follow the reductions, hash layout only
+  MREC_CHECK_REQ(req, (reinterpret_cast<uintptr_t>(req.sgd_table) & 15) == 0,
+                 "sgd table not 16-B aligned");
+  MREC_CHECK_REQ(req, req.sgd_blocks >= 0 && (req.sgd_blocks == 0 || req.sgd_table != nullptr),
+                 "sgd_blocks > 0 needs the table");
+  MREC_CHECK_REQ(req, req.sgd_blocks == 0 || hash, "SGD tiles ride in the hash-layout apply only");
+  x.a.sgd = static_cast<const SgdArgs *>(req.sgd_table);
+  x.a.sgd_blocks = req.sgd_blocks;
+  const int wpb = 256 / lpr;
+  // hash layout (batch <= kHashMaxKeys or an exchange view, see mrec_emb_bwd_plan):
+  // sample-major blocks + one hot-segment block per (table, bucket); sorted
+  // layout: one block per WPB segments of each table
+  x.seg_blocks = hash ? (batch > 0 ? F * kPlanBuckets : 0)
+                      : static_cast<int>((batch + wpb - 1) / wpb);
+  x.sm_blocks = hash ? static_cast<int>((batch * F + wpb - 1) / wpb) : 0;
+  x.apply_blocks = hash ? x.seg_blocks * (1 + kHotPer) + x.sm_blocks : x.seg_blocks * F;
+  int co_blocks = 0;
+  if ((st = build_co_reduce(req.n_reduce, req.reduce, &x.co, &co_blocks)) != MREC_OK) return st;
+  co_blocks += req.sgd_blocks;
+  if (x.apply_blocks + co_blocks == 0) return MREC_OK;  // (batch 0 still runs the reductions)
+  x.ba = ba;
+  x.batch = batch;
+  x.ws = workspace;
+  x.grid = dim3(static_cast<unsigned>(x.apply_blocks + co_blocks));
+  x.kc = hash && !req.bag ? kclock_take() : KClock{nullptr, 0};  // (bags: unclocked)
+  x.s = static_cast<hipStream_t>(stream);
+  if (!req.bag)
+    launch_apply<false>(bank->dtype, lpr, hash, x);
+  else
+    launch_apply<true>(bank->dtype, lpr, hash, x);
+  return launch_status("mrec_emb_bwd_apply");
+}
 
 extern "C" {
 
@@ -889,9 +973,12 @@ mrec_status mrec_emb_bwd_apply(const mrec_table_bank *bank, int64_t batch, const
                                mrec_dtype x0_dtype, int64_t x0_ld, const float *dw,
                                mrec_bwd_mode mode, float lr, uint64_t seed,
                                const uint64_t *d_step, void *grad, mrec_stream stream) {
-  return apply_impl(bank, batch, workspace, ws_bytes, dx, dx_dtype, dx_ld, dfm, fm_sum, x0,
-                    x0_dtype, x0_ld, dw, nullptr, 0, 0, 0, mode, lr, seed, d_step, grad, 0,
-                    nullptr, stream);
+  BwdRequest r;
+  r.who = __func__;
+  r.dx = dx, r.dx_dtype = dx_dtype, r.dx_ld = dx_ld, r.dfm = dfm, r.fm_sum = fm_sum;
+  r.x0 = x0, r.x0_dtype = x0_dtype, r.x0_ld = x0_ld, r.dw = dw;
+  r.mode = mode, r.lr = lr, r.seed = seed, r.d_step = d_step, r.grad = grad;
+  return apply_request(bank, batch, workspace, ws_bytes, stream, r);
 }
 
 mrec_status mrec_emb_bwd_apply_ex(const mrec_table_bank *bank, int64_t batch,
@@ -902,9 +989,13 @@ mrec_status mrec_emb_bwd_apply_ex(const mrec_table_bank *bank, int64_t batch,
                                   uint64_t seed, const uint64_t *d_step, void *grad,
                                   int32_t n_reduce, const mrec_gemm_call *reduce,
                                   mrec_stream stream) {
-  return apply_impl(bank, batch, workspace, ws_bytes, dx, dx_dtype, dx_ld, dfm, fm_sum, x0,
-                    x0_dtype, x0_ld, dw, nullptr, 0, 0, 0, mode, lr, seed, d_step, grad, n_reduce,
-                    reduce, stream);
+  BwdRequest r;
+  r.who = __func__;
+  r.dx = dx, r.dx_dtype = dx_dtype, r.dx_ld = dx_ld, r.dfm = dfm, r.fm_sum = fm_sum;
+  r.x0 = x0, r.x0_dtype = x0_dtype, r.x0_ld = x0_ld, r.dw = dw;
+  r.mode = mode, r.lr = lr, r.seed = seed, r.d_step = d_step, r.grad = grad;
+  r.n_reduce = n_reduce, r.reduce = reduce;
+  return apply_request(bank, batch, workspace, ws_bytes, stream, r);
 }
 
 mrec_status mrec_emb_bwd_apply_bag(const mrec_table_bank *bank, int64_t batch,
@@ -915,14 +1006,14 @@ mrec_status mrec_emb_bwd_apply_bag(const mrec_table_bank *bank, int64_t batch,
                                    uint64_t seed, const uint64_t *d_step, void *grad,
                                    int32_t n_reduce, const mrec_gemm_call *reduce,
                                    mrec_stream stream, int32_t bag_len, const float *bag_scale) {
-  MREC_CHECK_ARG(bag_len >= 1, "bag_len < 1");
-  MREC_CHECK_ARG(batch >= 0 && batch % bag_len == 0, "batch is not a multiple of bag_len");
-  MREC_CHECK_ARG(bag_scale != nullptr, "bag_scale is NULL");
-  MREC_CHECK_ARG(dfm == nullptr, "the FM term is undefined for bags (dfm must be NULL)");
-  const BagGrad bg{bag_len, bag_scale};
-  return apply_impl(bank, batch, workspace, ws_bytes, dx, dx_dtype, dx_ld, dfm, fm_sum, x0,
-                    x0_dtype, x0_ld, dw, nullptr, 0, 0, 0, mode, lr, seed, d_step, grad, n_reduce,
-                    reduce, stream, nullptr, nullptr, nullptr, 0, &bg);
+  BwdRequest r;
+  r.who = __func__;
+  r.dx = dx, r.dx_dtype = dx_dtype, r.dx_ld = dx_ld, r.dfm = dfm, r.fm_sum = fm_sum;
+  r.x0 = x0, r.x0_dtype = x0_dtype, r.x0_ld = x0_ld, r.dw = dw;
+  r.mode = mode, r.lr = lr, r.seed = seed, r.d_step = d_step, r.grad = grad;
+  r.n_reduce = n_reduce, r.reduce = reduce;
+  r.bag = true, r.bag_len = bag_len, r.bag_scale = bag_scale;
+  return apply_request(bank, batch, workspace, ws_bytes, stream, r);
 }
 
 mrec_status mrec_emb_bwd_apply_given(const mrec_table_bank *bank, int64_t batch,
@@ -934,9 +1025,14 @@ mrec_status mrec_emb_bwd_apply_given(const mrec_table_bank *bank, int64_t batch,
                                      mrec_bwd_mode mode, float lr, uint64_t seed,
                                      const uint64_t *d_step, void *grad, int32_t n_reduce,
                                      const mrec_gemm_call *reduce, mrec_stream stream) {
-  return apply_impl(bank, batch, workspace, ws_bytes, dx, dx_dtype, dx_ld, dfm, fm_sum, x0,
-                    x0_dtype, x0_ld, dw, g_occ, g_ld, chunk, chunk_stride, mode, lr, seed, d_step,
-                    grad, n_reduce, reduce, stream);
+  BwdRequest r;
+  r.who = __func__;
+  r.dx = dx, r.dx_dtype = dx_dtype, r.dx_ld = dx_ld, r.dfm = dfm, r.fm_sum = fm_sum;
+  r.x0 = x0, r.x0_dtype = x0_dtype, r.x0_ld = x0_ld, r.dw = dw;
+  r.g_occ = g_occ, r.g_ld = g_ld, r.chunk = chunk, r.chunk_stride = chunk_stride;
+  r.mode = mode, r.lr = lr, r.seed = seed, r.d_step = d_step, r.grad = grad;
+  r.n_reduce = n_reduce, r.reduce = reduce;
+  return apply_request(bank, batch, workspace, ws_bytes, stream, r);
 }
 
 mrec_status mrec_emb_bwd_apply_rec(const mrec_table_bank *bank, int64_t batch,
@@ -947,11 +1043,14 @@ mrec_status mrec_emb_bwd_apply_rec(const mrec_table_bank *bank, int64_t batch,
                                    int32_t n_reduce, const mrec_gemm_call *reduce,
                                    mrec_stream stream) {
   MREC_CHECK_ARG(out != nullptr, "out is NULL");
-  MREC_CHECK_ARG(out->rec_bytes > 0 && out->rec_bytes % 4 == 0, "bad record bytes");
-  const RecOut ro{out->wire, out->rec_bytes / 4, out->pref, out->cap, out->cap_rows};
-  return apply_impl(bank, batch, workspace, ws_bytes, dx, dx_dtype, dx_ld, dfm, fm_sum, x0,
-                    x0_dtype, x0_ld, dw, nullptr, 0, 0, 0, MREC_BWD_DENSE_GRAD, 0.f, 0, nullptr,
-                    nullptr, n_reduce, reduce, stream, nullptr, &ro);
+  BwdRequest r;
+  r.who = __func__;
+  r.dx = dx, r.dx_dtype = dx_dtype, r.dx_ld = dx_ld, r.dfm = dfm, r.fm_sum = fm_sum;
+  r.x0 = x0, r.x0_dtype = x0_dtype, r.x0_ld = x0_ld, r.dw = dw;
+  r.rec_out = out;
+  r.mode = MREC_BWD_DENSE_GRAD;
+  r.n_reduce = n_reduce, r.reduce = reduce;
+  return apply_request(bank, batch, workspace, ws_bytes, stream, r);
 }
 
 mrec_status mrec_emb_bwd_apply_wire(const mrec_table_bank *bank, int64_t batch,
@@ -961,13 +1060,13 @@ mrec_status mrec_emb_bwd_apply_wire(const mrec_table_bank *bank, int64_t batch,
                                     mrec_bwd_mode mode, float lr, uint64_t seed,
                                     const uint64_t *d_step, void *grad, int32_t n_reduce,
                                     const mrec_gemm_call *reduce, mrec_stream stream) {
-  MREC_CHECK_ARG(wire_dtype == MREC_BF16 || wire_dtype == MREC_F32, "wire dtype must be BF16/F32");
-  const int es = wire_dtype == MREC_BF16 ? 2 : 4;
-  MREC_CHECK_ARG(rec_bytes > 0 && rec_bytes % es == 0 && rec_bytes % 4 == 0, "bad record bytes");
-  const GivenWire gw{wire, wire_dtype == MREC_BF16 ? 1 : 0, rec_bytes / es, pref, cap_rows};
-  return apply_impl(bank, batch, workspace, ws_bytes, nullptr, MREC_F32, 0, nullptr, nullptr,
-                    nullptr, MREC_F32, 0, nullptr, nullptr, 0, chunk, chunk_stride, mode, lr, seed,
-                    d_step, grad, n_reduce, reduce, stream, &gw);
+  BwdRequest r;
+  r.who = __func__;
+  r.from_wire = true, r.wire = wire, r.rec_bytes = rec_bytes, r.wire_dtype = wire_dtype;
+  r.pref = pref, r.cap_rows = cap_rows, r.chunk = chunk, r.chunk_stride = chunk_stride;
+  r.mode = mode, r.lr = lr, r.seed = seed, r.d_step = d_step, r.grad = grad;
+  r.n_reduce = n_reduce, r.reduce = reduce;
+  return apply_request(bank, batch, workspace, ws_bytes, stream, r);
 }
 
 mrec_status mrec_emb_bwd_apply_wire_sgd(const mrec_table_bank *bank, int64_t batch,
@@ -979,228 +1078,14 @@ mrec_status mrec_emb_bwd_apply_wire_sgd(const mrec_table_bank *bank, int64_t bat
                                         int32_t n_reduce, const mrec_gemm_call *reduce,
                                         const void *sgd_table, int32_t sgd_blocks,
                                         mrec_stream stream) {
-  MREC_CHECK_ARG(wire_dtype == MREC_BF16 || wire_dtype == MREC_F32, "wire dtype must be BF16/F32");
-  const int es = wire_dtype == MREC_BF16 ? 2 : 4;
-  MREC_CHECK_ARG(rec_bytes > 0 && rec_bytes % es == 0 && rec_bytes % 4 == 0, "bad record bytes");
-  MREC_CHECK_ARG(sgd_table == nullptr || (reinterpret_cast<uintptr_t>(sgd_table) & 15) == 0,
-                 "sgd table not 16-B aligned");
-  const GivenWire gw{wire, wire_dtype == MREC_BF16 ? 1 : 0, rec_bytes / es, pref, cap_rows};
-  return apply_impl(bank, batch, workspace, ws_bytes, nullptr, MREC_F32, 0, nullptr, nullptr,
-                    nullptr, MREC_F32, 0, nullptr, nullptr, 0, chunk, chunk_stride, mode, lr, seed,
-                    d_step, grad, n_reduce, reduce, stream, &gw, nullptr, sgd_table, sgd_blocks);
+  BwdRequest r;
+  r.who = __func__;
+  r.from_wire = true, r.wire = wire, r.rec_bytes = rec_bytes, r.wire_dtype = wire_dtype;
+  r.pref = pref, r.cap_rows = cap_rows, r.chunk = chunk, r.chunk_stride = chunk_stride;
+  r.mode = mode, r.lr = lr, r.seed = seed, r.d_step = d_step, r.grad = grad;
+  r.n_reduce = n_reduce, r.reduce = reduce;
+  r.sgd_table = sgd_table, r.sgd_blocks = sgd_blocks;
+  return apply_request(bank, batch, workspace, ws_bytes, stream, r);
 }
 
 }  // extern "C"
-
-static mrec_status apply_impl(const mrec_table_bank *bank, int64_t batch, const void *workspace,
-                              size_t ws_bytes, const void *dx, mrec_dtype dx_dtype, int64_t dx_ld,
-                              const float *dfm, const float *fm_sum, const void *x0,
-                              mrec_dtype x0_dtype, int64_t x0_ld, const float *dw,
-                              const float *g_occ, int64_t g_ld, int64_t chunk,
-                              int64_t chunk_stride, mrec_bwd_mode mode, float lr, uint64_t seed,
-                              const uint64_t *d_step, void *grad, int32_t n_reduce,
-                              const mrec_gemm_call *reduce, mrec_stream stream,
-                              const GivenWire *gw, const RecOut *ro, const void *sgd_table,
-                              int32_t sgd_blocks, const BagGrad *bag) {
-  BankArgs ba;
-  int eb, lpr;
-  mrec_status st = make_bank_args(bank, &ba, &eb, &lpr);
-  if (st != MREC_OK) return st;
-  MREC_CHECK_ARG(batch >= 0 && batch <= kMaxPlanKeys, "batch must be in [0, MREC_BWD_MAX_BATCH]");
-  MREC_CHECK_ARG(workspace != nullptr, "workspace is NULL");
-  if (ws_bytes < mrec_emb_bwd_workspace_size(ba.n_tables, batch)) {
-    set_error("mrec_emb_bwd_apply: workspace too small");
-    return MREC_ENOSPC;
-  }
-  MREC_CHECK_ARG(mode >= MREC_BWD_DENSE_GRAD && mode <= MREC_BWD_ADAM, "bad mode");
-  // the layout this apply reads (hash: batch <= 4096, or an exchange view's given
-  // gradients up to 8192 entries) must be the one the workspace's plan wrote
-  const bool hash = hash_layout(batch, g_occ != nullptr || gw != nullptr);
-  if ((st = ws_layout_check(workspace, hash ? kLayoutHash : kLayoutSorted, batch, ba.n_tables,
-                            gw ? "mrec_emb_bwd_apply_wire"
-                               : bag ? "mrec_emb_bwd_apply_bag"
-                               : ro ? "mrec_emb_bwd_apply_rec"
-                                    : g_occ ? "mrec_emb_bwd_apply_given" : "mrec_emb_bwd_apply")) !=
-      MREC_OK)
-    return st;
-  MREC_CHECK_ARG(mode != MREC_BWD_DENSE_GRAD || grad != nullptr || ro != nullptr,
-                 "DENSE_GRAD needs grad");
-  if (ro) {
-    MREC_CHECK_ARG(mode == MREC_BWD_DENSE_GRAD && grad == nullptr, "records take DENSE_GRAD sums");
-    MREC_CHECK_ARG(hash_layout(batch, false), "record output needs the hash layout (batch <= 4096)");
-    MREC_CHECK_ARG(ro->wire && ro->pref && ro->cap >= 1 && ro->cap_rows >= 1 &&
-                       (reinterpret_cast<uintptr_t>(ro->wire) & 3) == 0,
-                   "records: NULL wire / pref, bad cap");
-    MREC_CHECK_ARG(ro->rec_dw * 4 >= (ba.dim + (ba.has_w ? 1 : 0)) * eb, "record narrower than a row");
-    grad = bank->data;  // (the raw loads of the old sums read the rows: never used)
-  }
-  OptArgs opt{};
-  if ((st = make_opt_args(bank, mode, &opt)) != MREC_OK) return st;
-  const int F = ba.n_tables, D = ba.dim;
-  if (dx) {
-    MREC_CHECK_ARG(dx_dtype == MREC_F32 || dx_dtype == MREC_BF16, "dx dtype must be F32/BF16");
-    const int xb = dx_dtype == MREC_F32 ? 4 : 2;
-    MREC_CHECK_ARG(dx_ld >= static_cast<int64_t>(F) * D, "dx_ld < F*dim");
-    MREC_CHECK_ARG((reinterpret_cast<uintptr_t>(dx) & 15) == 0 && (dx_ld * xb) % 16 == 0,
-                   "dx must be 16B aligned with 16B-multiple rows");
-  }
-  if (dfm) {
-    MREC_CHECK_ARG(fm_sum != nullptr && x0 != nullptr, "dfm needs fm_sum and x0");
-    MREC_CHECK_ARG(x0_dtype == MREC_F32 || x0_dtype == MREC_BF16, "x0 dtype must be F32/BF16");
-    const int xb = x0_dtype == MREC_F32 ? 4 : 2;
-    MREC_CHECK_ARG(x0_ld >= static_cast<int64_t>(F) * D, "x0_ld < F*dim");
-    MREC_CHECK_ARG((reinterpret_cast<uintptr_t>(x0) & 15) == 0 && (x0_ld * xb) % 16 == 0 &&
-                       (reinterpret_cast<uintptr_t>(fm_sum) & 15) == 0,
-                   "x0/fm_sum must be 16B aligned with 16B-multiple rows");
-  }
-  MREC_CHECK_ARG(dw == nullptr || ba.has_w, "dw given but bank has no w column");
-  if (gw) {
-    MREC_CHECK_ARG(!dx && !dfm && !dw && !g_occ, "wire gradients exclude dx / dfm / dw / g_occ");
-    MREC_CHECK_ARG(gw->wire && gw->pref && gw->cap_rows >= 1, "NULL wire / pref");
-    MREC_CHECK_ARG(gw->pitch >= D + (ba.has_w ? 1 : 0) && (gw->pitch * (gw->bf16 ? 2 : 4)) % 4 == 0 &&
-                       (reinterpret_cast<uintptr_t>(gw->wire) & 3) == 0,
-                   "records: pitch >= dim + has_w elements, 4-B aligned");
-    MREC_CHECK_ARG(chunk >= 1 && chunk_stride >= F * chunk, "bad chunk");
-  }
-  if (g_occ) {
-    MREC_CHECK_ARG(!dx && !dfm && !dw, "g_occ excludes dx / dfm / dw");
-    MREC_CHECK_ARG(g_ld >= D + (ba.has_w ? 1 : 0) && g_ld % 4 == 0 &&
-                       (reinterpret_cast<uintptr_t>(g_occ) & 15) == 0,
-                   "g_occ rows must be 16B aligned, g_ld >= dim + has_w, g_ld % 4 == 0");
-    MREC_CHECK_ARG(chunk >= 0 && (chunk == 0 || chunk_stride >= F * chunk), "bad chunk");
-  }
-  ApplyArgs a{};
-  a.dx = dx;
-  a.dx_ld = dx_ld;
-  a.dx_bf16 = dx_dtype == MREC_BF16;
-  a.dfm = dfm;
-  a.fm_sum = fm_sum;
-  a.x0 = x0;
-  a.x0_ld = x0_ld;
-  a.x0_bf16 = x0_dtype == MREC_BF16;
-  a.dw = dw;
-  a.mode = mode;
-  a.lr = lr;
-  a.seed = seed;
-  a.d_step = d_step;
-  a.grad = grad;
-  a.g_occ = g_occ;
-  a.g_ld = g_ld;
-  a.chunk = chunk;
-  a.chunk_stride = chunk_stride;
-  a.g_rec = gw ? gw->wire : nullptr;
-  a.g_rec_bf16 = gw ? gw->bf16 : 0;
-  a.g_rec_pitch = gw ? gw->pitch : 0;
-  a.g_pref = gw ? gw->pref : nullptr;
-  a.g_cap_rows = gw ? gw->cap_rows : 0;
-  a.g_F = F;
-  a.opt = opt;
-  a.o_rec = ro ? static_cast<uint32_t *>(ro->wire) : nullptr;
-  a.o_rec_dw = ro ? ro->rec_dw : 0;
-  a.o_pref = ro ? ro->pref : nullptr;
-  a.o_F = F;
-  a.o_cap = ro ? ro->cap : 1;
-  a.o_cap_rows = ro ? ro->cap_rows : 0;
-  MREC_CHECK_ARG(sgd_blocks >= 0 && (sgd_blocks == 0 || sgd_table != nullptr),
-                 "sgd_blocks > 0 needs the table");
-  a.sgd = static_cast<const SgdArgs *>(sgd_table);
-  a.sgd_blocks = sgd_blocks;
-  a.bag = bag ? bag->bag_len : 0;  // (dx / dw hold batch / bag_len rows: one per bag)
-  a.bag_scale = bag ? bag->scale : nullptr;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int wpb = 256 / lpr;
-  // hash layout (batch <= kHashMaxKeys or an exchange view, see mrec_emb_bwd_plan):
-  // sample-major blocks + one hot-segment block per (table, bucket); sorted
-  // layout: one block per WPB segments of each table
-  const int seg_blocks = hash ? (batch > 0 ? F * kPlanBuckets : 0)
-                              : static_cast<int>((batch + wpb - 1) / wpb);
-  const int64_t sm_blocks = hash ? (batch * F + wpb - 1) / wpb : 0;
-  const int apply_blocks =
-      static_cast<int>(hash ? seg_blocks * (1 + kHotPer) + sm_blocks
-                           : static_cast<int64_t>(seg_blocks) * F);
-  CoReduce co = {};
-  int co_blocks = 0;
-  if (mrec_status st = build_co_reduce(n_reduce, reduce, &co, &co_blocks); st != MREC_OK)
-    return st;
-  co_blocks += sgd_blocks;  // (the SGD tiles follow the reductions, hash layout only)
-  MREC_CHECK_ARG(sgd_blocks == 0 || hash, "SGD tiles ride in the hash-layout apply only");
-  if (apply_blocks + co_blocks == 0) return MREC_OK;  // (batch 0 still runs the reductions)
-  const dim3 grid(static_cast<unsigned>(apply_blocks + co_blocks));
-  const KClock kc = hash && !bag ? kclock_take() : KClock{nullptr, 0};  // (bags: unclocked)
-#define MREC_AKM(T, L, M)                                                                         \
-  do {                                                                                            \
-    if (kc.buf)                                                                                   \
-      apply_hash_kernel<T, L, M, true><<<grid, 256, 0, s>>>(ba, batch, workspace, a, seg_blocks,  \
-                                                            static_cast<int>(sm_blocks), co, kc); \
-    else                                                                                          \
-      apply_hash_kernel<T, L, M, false><<<grid, 256, 0, s>>>(ba, batch, workspace, a, seg_blocks, \
-                                                             static_cast<int>(sm_blocks), co, kc); \
-  } while (0)
-#define MREC_AK(T, L)                                                                            \
-  do {                                                                                           \
-    if (hash) {                                                                                  \
-      if (mode == MREC_BWD_SGD) MREC_AKM(T, L, MREC_BWD_SGD);                                    \
-      else if (mode == MREC_BWD_SGD_SR) MREC_AKM(T, L, MREC_BWD_SGD_SR);                         \
-      else if (mode == MREC_BWD_DENSE_GRAD) MREC_AKM(T, L, MREC_BWD_DENSE_GRAD);                 \
-      else MREC_AKM(T, L, -1); /* fused optimizers */                                            \
-    } else                                                                                       \
-      apply_kernel<T, L><<<grid, 256, 0, s>>>(ba, batch, workspace, a, seg_blocks, apply_blocks, \
-                                              co);                                               \
-  } while (0)
-  // the bag-indirection instantiations (mrec_emb_bwd_apply_bag only, unclocked):
-  // dispatched after every other kernel of the file, whose layout they leave alone
-#define MREC_BKM(T, L, M)                                      \
-  apply_hash_kernel<T, L, M, false, true><<<grid, 256, 0, s>>>( \
-      ba, batch, workspace, a, seg_blocks, static_cast<int>(sm_blocks), co, kc)
-#define MREC_BK(T, L)                                                                          \
-  do {                                                                                         \
-    if (hash) {                                                                                \
-      if (mode == MREC_BWD_SGD) MREC_BKM(T, L, MREC_BWD_SGD);                                  \
-      else if (mode == MREC_BWD_SGD_SR) MREC_BKM(T, L, MREC_BWD_SGD_SR);                       \
-      else if (mode == MREC_BWD_DENSE_GRAD) MREC_BKM(T, L, MREC_BWD_DENSE_GRAD);               \
-      else MREC_BKM(T, L, -1);                                                                 \
-    } else                                                                                     \
-      apply_kernel<T, L, true><<<grid, 256, 0, s>>>(ba, batch, workspace, a, seg_blocks,       \
-                                                    apply_blocks, co);                         \
-  } while (0)
-  if (!bag) {
-    if (bank->dtype == MREC_BF16) {
-      switch (lpr) {
-        case 1: MREC_AK(uint16_t, 1); break;
-        case 2: MREC_AK(uint16_t, 2); break;
-        case 4: MREC_AK(uint16_t, 4); break;
-        case 8: MREC_AK(uint16_t, 8); break;
-        default: MREC_AK(uint16_t, 16); break;
-      }
-    } else {
-      switch (lpr) {
-        case 1: MREC_AK(float, 1); break;
-        case 2: MREC_AK(float, 2); break;
-        case 4: MREC_AK(float, 4); break;
-        case 8: MREC_AK(float, 8); break;
-        default: MREC_AK(float, 16); break;
-      }
-    }
-  } else if (bank->dtype == MREC_BF16) {
-    switch (lpr) {
-      case 1: MREC_BK(uint16_t, 1); break;
-      case 2: MREC_BK(uint16_t, 2); break;
-      case 4: MREC_BK(uint16_t, 4); break;
-      case 8: MREC_BK(uint16_t, 8); break;
-      default: MREC_BK(uint16_t, 16); break;
-    }
-  } else {
-    switch (lpr) {
-      case 1: MREC_BK(float, 1); break;
-      case 2: MREC_BK(float, 2); break;
-      case 4: MREC_BK(float, 4); break;
-      case 8: MREC_BK(float, 8); break;
-      default: MREC_BK(float, 16); break;
-    }
-  }
-#undef MREC_BK
-#undef MREC_BKM
-#undef MREC_AK
-#undef MREC_AKM
-  return launch_status("mrec_emb_bwd_apply");
-}

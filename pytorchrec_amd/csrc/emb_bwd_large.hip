@@ -1439,66 +1439,32 @@ mrec_status mrec_emb_bwd_large_plan(const mrec_table_bank *bank, const mrec_ids 
 
 }  // extern "C"
 
-// the apply arguments, checked (shared by mrec_emb_bwd_large_apply / _fused)
-static mrec_status lg_apply_args(const mrec_table_bank *bank, const BankArgs &ba, const void *dx,
-                                 mrec_dtype dx_dtype, int64_t dx_ld, const float *dfm,
-                                 const float *fm_sum, const void *x0, mrec_dtype x0_dtype,
-                                 int64_t x0_ld, const float *dw, mrec_bwd_mode mode, float lr,
-                                 uint64_t seed, const uint64_t *d_step, void *grad, ApplyArgs *out) {
-  MREC_CHECK_ARG(mode >= MREC_BWD_DENSE_GRAD && mode <= MREC_BWD_ADAM, "bad mode");
-  OptArgs opt{};
-  {
-    const mrec_status so = make_opt_args(bank, mode, &opt);
-    if (so != MREC_OK) return so;
-  }
-  MREC_CHECK_ARG(mode != MREC_BWD_DENSE_GRAD || grad != nullptr, "DENSE_GRAD needs grad");
-  const int F = ba.n_tables, D = ba.dim;
-  if (dx) {
-    MREC_CHECK_ARG(dx_dtype == MREC_F32 || dx_dtype == MREC_BF16, "dx dtype must be F32/BF16");
-    const int xb = dx_dtype == MREC_F32 ? 4 : 2;
-    MREC_CHECK_ARG(dx_ld >= static_cast<int64_t>(F) * D, "dx_ld < F*dim");
-    MREC_CHECK_ARG((reinterpret_cast<uintptr_t>(dx) & 15) == 0 && (dx_ld * xb) % 16 == 0,
-                   "dx must be 16B aligned with 16B-multiple rows");
-  }
-  if (dfm) {
-    MREC_CHECK_ARG(fm_sum != nullptr && x0 != nullptr, "dfm needs fm_sum and x0");
-    MREC_CHECK_ARG(x0_dtype == MREC_F32 || x0_dtype == MREC_BF16, "x0 dtype must be F32/BF16");
-    const int xb = x0_dtype == MREC_F32 ? 4 : 2;
-    MREC_CHECK_ARG(x0_ld >= static_cast<int64_t>(F) * D, "x0_ld < F*dim");
-    MREC_CHECK_ARG((reinterpret_cast<uintptr_t>(x0) & 15) == 0 && (x0_ld * xb) % 16 == 0 &&
-                       (reinterpret_cast<uintptr_t>(fm_sum) & 15) == 0,
-                   "x0/fm_sum must be 16B aligned with 16B-multiple rows");
-  }
-  MREC_CHECK_ARG(dw == nullptr || ba.has_w, "dw given but bank has no w column");
-  ApplyArgs a = {};
-  a.dx = dx;
-  a.dx_ld = dx_ld;
-  a.dx_bf16 = dx_dtype == MREC_BF16;
-  a.dfm = dfm;
-  a.fm_sum = fm_sum;
-  a.x0 = x0;
-  a.x0_ld = x0_ld;
-  a.x0_bf16 = x0_dtype == MREC_BF16;
-  a.dw = dw;
-  a.mode = mode;
-  a.lr = lr;
-  a.seed = seed;
-  a.d_step = d_step;
-  a.opt = opt;
-  a.grad = grad;
-  *out = a;
-  return MREC_OK;
-}
+// one large-batch apply: what the chunked kernels and the per-row apply are given
+struct LgLaunch {
+  BankArgs ba;
+  int64_t batch;
+  LgWs w;
+  ApplyArgs a;
+  int fused_nb = 0, G = 0, lognb = 0;  // fused: the bucket kernel first (NB buckets, G groups)
+  CoReduce co = {};
+  int co_blocks = 0;
+  hipStream_t s;
+};
 
 // the chunked kernels and the per-row apply (fused: the bucket kernel first, the
 // per-row apply then walks only the huge segments' slots)
 template <typename T, int L, bool BAG = false>
-static void lg_launch_apply(const BankArgs &ba, int64_t batch, const LgWs &w, const ApplyArgs &a,
-                            int stride, int fused_nb, int G, int lognb, const CoReduce &co,
-                            int co_blocks, hipStream_t s) {
+static void lg_launch_apply(const LgLaunch &x) {
+  const BankArgs &ba = x.ba;
+  const int64_t batch = x.batch;
+  const LgWs &w = x.w;
+  const ApplyArgs &a = x.a;
+  const int stride = ba.row_stride;
+  hipStream_t s = x.s;
   dim3 gc(kLgApplyBlocks), gu(kLgApplyBlocks);
-  if (fused_nb) {
-    bk_apply_kernel<T, L, BAG><<<dim3(fused_nb + co_blocks), 256, 0, s>>>(ba, w, a, G, lognb, co);
+  if (x.fused_nb) {
+    bk_apply_kernel<T, L, BAG><<<dim3(x.fused_nb + x.co_blocks), 256, 0, s>>>(ba, w, a, x.G,
+                                                                             x.lognb, x.co);
     // only huge segments are left: as many workgroups as their slots (mostly holes)
     const int64_t N = batch * ba.n_tables;
     const int64_t ul = (N + kLgHuge) / (kLgHuge + 1) + 1;
@@ -1529,39 +1495,76 @@ static void lg_launch_apply(const BankArgs &ba, int64_t batch, const LgWs &w, co
   lg_apply_kernel<T, L, BAG><<<gu, 256, 0, s>>>(ba, batch, w, a, stride);
 }
 
-static void lg_dispatch_apply_bag(mrec_dtype dtype, int lpr, const BankArgs &ba, int64_t batch,
-                                  const LgWs &w, const ApplyArgs &a, int stride, int fused_nb,
-                                  int G, int lognb, hipStream_t s, const CoReduce &co,
-                                  int co_blocks);
+// (defined last in the file: the bag instantiations follow every other kernel)
+static void lg_dispatch_apply_bag(mrec_dtype dtype, int lpr, const LgLaunch &x);
 
-static void lg_dispatch_apply(mrec_dtype dtype, int lpr, const BankArgs &ba, int64_t batch,
-                              const LgWs &w, const ApplyArgs &a, int stride, int fused_nb, int G,
-                              int lognb, hipStream_t s, const CoReduce &co = CoReduce{},
-                              int co_blocks = 0) {
-  if (a.bag) {  // the bag-indirection instantiations (below: they follow every other kernel)
-    lg_dispatch_apply_bag(dtype, lpr, ba, batch, w, a, stride, fused_nb, G, lognb, s, co, co_blocks);
-    return;
-  }
-#define MREC_LG(T, L) \
-  lg_launch_apply<T, L>(ba, batch, w, a, stride, fused_nb, G, lognb, co, co_blocks, s)
-  if (dtype == MREC_BF16) {
-    switch (lpr) {
-      case 1: MREC_LG(uint16_t, 1); break;
-      case 2: MREC_LG(uint16_t, 2); break;
-      case 4: MREC_LG(uint16_t, 4); break;
-      case 8: MREC_LG(uint16_t, 8); break;
-      default: MREC_LG(uint16_t, 16); break;
+static void lg_dispatch_apply(mrec_dtype dtype, int lpr, const LgLaunch &x) {
+  if (x.a.bag) return lg_dispatch_apply_bag(dtype, lpr, x);
+  for_row_geometry(dtype, lpr, [&](auto t, auto l) {
+    lg_launch_apply<decltype(t), decltype(l)::value>(x);
+  });
+}
+
+// mrec_emb_bwd_large_apply: the apply of a workspace mrec_emb_bwd_large_plan filled
+static mrec_status lg_apply_request(const mrec_table_bank *bank, int64_t batch, void *workspace,
+                                    size_t ws_bytes, mrec_stream stream, const BwdRequest &req) {
+  LgLaunch x;
+  int lpr;
+  int64_t R;
+  mrec_status st = lg_setup(bank, batch, workspace, ws_bytes, &x.ba, &lpr, &R, &x.w);
+  if (st != MREC_OK) return st;
+  if ((st = make_apply_args(bank, x.ba, batch, req, &x.a)) != MREC_OK) return st;
+  if (batch == 0) return MREC_OK;
+  x.batch = batch;
+  x.s = static_cast<hipStream_t>(stream);
+  lg_dispatch_apply(bank->dtype, lpr, x);
+  return launch_status("mrec_emb_bwd_large_apply");
+}
+
+// every mrec_emb_bwd_large_fused* entry point: fused plan + apply of its request (own
+// gradients, or given ones: the owner side of a row-sharded exchange)
+static mrec_status lg_fused_request(const mrec_table_bank *bank, const mrec_ids *ids,
+                                    int64_t batch, void *workspace, size_t ws_bytes,
+                                    int32_t *d_oob_flag, mrec_stream stream,
+                                    const BwdRequest &req) {
+  LgLaunch x;
+  IdsArgs ia;
+  int es = 0, lpr = 0;
+  int64_t R;
+  mrec_status st = make_bank_args(bank, &x.ba, &es, &lpr);
+  if (st != MREC_OK) return st;
+  if ((st = make_apply_args(bank, x.ba, batch, req, &x.a)) != MREC_OK) return st;
+  // (an exchange view always has parts: chunk == 0 is the batched path's unchunked g_occ)
+  MREC_CHECK_REQ(req, !(req.g_occ || req.from_wire) || req.chunk >= 1,
+                 "chunk (entries per exchange part) must be >= 1");
+  st = lg_setup(bank, batch, workspace, ws_bytes, &x.ba, &lpr, &R, &x.w);
+  if (st != MREC_OK) return st;
+  if ((st = make_ids_args(ids, x.ba.n_tables, &ia)) != MREC_OK) return st;
+  if ((st = build_co_reduce(req.n_reduce, req.reduce, &x.co, &x.co_blocks)) != MREC_OK) return st;
+  x.batch = batch;
+  x.s = static_cast<hipStream_t>(stream);
+  const int64_t total = batch * x.ba.n_tables;
+  const int G = batch == 0 ? 0 : bk_groups(R, total);
+  if (G == 0 || (std::getenv("MREC_LG_ATOMIC_PLAN") && R <= kLgMaxRows)) {  // the two-call path
+    const int n_co = x.co.n;
+    if (batch > 0) {
+      st = mrec_emb_bwd_large_plan(bank, ids, batch, workspace, ws_bytes, d_oob_flag, stream);
+      if (st != MREC_OK) return st;
+      x.co = CoReduce{};  // (the reductions run as their own launch below)
+      x.co_blocks = 0;
+      lg_dispatch_apply(bank->dtype, lpr, x);
+      if ((st = launch_status("mrec_emb_bwd_large_apply")) != MREC_OK) return st;
     }
-  } else {
-    switch (lpr) {
-      case 1: MREC_LG(float, 1); break;
-      case 2: MREC_LG(float, 2); break;
-      case 4: MREC_LG(float, 4); break;
-      case 8: MREC_LG(float, 8); break;
-      default: MREC_LG(float, 16); break;
-    }
+    return n_co ? mrec_gemm_multi(req.n_reduce, req.reduce, stream) : MREC_OK;
   }
-#undef MREC_LG
+  const int NB = bk_buckets(total);
+  int lognb = 0;
+  while ((1 << lognb) < NB) ++lognb;
+  bk_hist_kernel<<<dim3(G), kBkThreads, 0, x.s>>>(x.ba, ia, batch, lognb, x.w, d_oob_flag);
+  bk_scatter_kernel<<<dim3(G), kBkThreads, 0, x.s>>>(x.ba, ia, batch, G, lognb, x.w, 1);
+  x.fused_nb = NB, x.G = G, x.lognb = lognb;
+  lg_dispatch_apply(bank->dtype, lpr, x);
+  return launch_status("mrec_emb_bwd_large_fused");
 }
 
 extern "C" {
@@ -1575,65 +1578,13 @@ mrec_status mrec_emb_bwd_large_apply(const mrec_table_bank *bank, int64_t batch,
                                      int64_t x0_ld, const float *dw, mrec_bwd_mode mode, float lr,
                                      uint64_t seed, const uint64_t *d_step, void *grad,
                                      mrec_stream stream) {
-  BankArgs ba;
-  int lpr;
-  int64_t R;
-  LgWs w;
-  mrec_status st = lg_setup(bank, batch, const_cast<void *>(workspace), ws_bytes, &ba, &lpr, &R,
-                            &w);
-  if (st != MREC_OK) return st;
-  ApplyArgs a{};
-  st = lg_apply_args(bank, ba, dx, dx_dtype, dx_ld, dfm, fm_sum, x0, x0_dtype, x0_ld, dw, mode,
-                     lr, seed, d_step, grad, &a);
-  if (st != MREC_OK) return st;
-  if (batch == 0) return MREC_OK;
-  lg_dispatch_apply(bank->dtype, lpr, ba, batch, w, a, ba.row_stride, 0, 0, 0,
-                    static_cast<hipStream_t>(stream));
-  return launch_status("mrec_emb_bwd_large_apply");
+  BwdRequest r;
+  r.who = __func__;
+  r.dx = dx, r.dx_dtype = dx_dtype, r.dx_ld = dx_ld, r.dfm = dfm, r.fm_sum = fm_sum;
+  r.x0 = x0, r.x0_dtype = x0_dtype, r.x0_ld = x0_ld, r.dw = dw;
+  r.mode = mode, r.lr = lr, r.seed = seed, r.d_step = d_step, r.grad = grad;
+  return lg_apply_request(bank, batch, const_cast<void *>(workspace), ws_bytes, stream, r);
 }
-
-}  // extern "C"
-
-// fused plan + apply with the apply arguments already built (own gradients, or
-// given ones: the owner side of a row-sharded exchange)
-static mrec_status lg_fused_impl(const mrec_table_bank *bank, const mrec_ids *ids, int64_t batch,
-                                 void *workspace, size_t ws_bytes, int32_t *d_oob_flag,
-                                 const ApplyArgs &a, int32_t n_reduce,
-                                 const mrec_gemm_call *reduce, mrec_stream stream) {
-  BankArgs ba;
-  IdsArgs ia;
-  int lpr;
-  int64_t R;
-  LgWs w;
-  mrec_status st = lg_setup(bank, batch, workspace, ws_bytes, &ba, &lpr, &R, &w);
-  if (st != MREC_OK) return st;
-  if ((st = make_ids_args(ids, ba.n_tables, &ia)) != MREC_OK) return st;
-  CoReduce co;
-  int co_blocks = 0;
-  if ((st = build_co_reduce(n_reduce, reduce, &co, &co_blocks)) != MREC_OK) return st;
-  const int64_t total = batch * ba.n_tables;
-  const int G = batch == 0 ? 0 : bk_groups(R, total);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (G == 0 || (std::getenv("MREC_LG_ATOMIC_PLAN") && R <= kLgMaxRows)) {  // the two-call path
-    if (batch > 0) {
-      st = mrec_emb_bwd_large_plan(bank, ids, batch, workspace, ws_bytes, d_oob_flag, stream);
-      if (st != MREC_OK) return st;
-      lg_dispatch_apply(bank->dtype, lpr, ba, batch, w, a, ba.row_stride, 0, 0, 0, s);
-      if ((st = launch_status("mrec_emb_bwd_large_apply")) != MREC_OK) return st;
-    }
-    return co.n ? mrec_gemm_multi(n_reduce, reduce, stream) : MREC_OK;
-  }
-  const int NB = bk_buckets(total);
-  int lognb = 0;
-  while ((1 << lognb) < NB) ++lognb;
-  bk_hist_kernel<<<dim3(G), kBkThreads, 0, s>>>(ba, ia, batch, lognb, w, d_oob_flag);
-  bk_scatter_kernel<<<dim3(G), kBkThreads, 0, s>>>(ba, ia, batch, G, lognb, w, 1);
-  lg_dispatch_apply(bank->dtype, lpr, ba, batch, w, a, ba.row_stride, NB, G, lognb, s, co,
-                    co_blocks);
-  return launch_status("mrec_emb_bwd_large_fused");
-}
-
-extern "C" {
 
 mrec_status mrec_emb_bwd_large_fused_ex(const mrec_table_bank *bank, const mrec_ids *ids,
                                         int64_t batch, void *workspace, size_t ws_bytes,
@@ -1644,17 +1595,13 @@ mrec_status mrec_emb_bwd_large_fused_ex(const mrec_table_bank *bank, const mrec_
                                         uint64_t seed, const uint64_t *d_step, void *grad,
                                         int32_t n_reduce, const mrec_gemm_call *reduce,
                                         mrec_stream stream) {
-  MREC_CHECK_ARG(bank != nullptr, "NULL bank");
-  BankArgs ba;
-  int es = 0, lpr = 0;
-  mrec_status st = make_bank_args(bank, &ba, &es, &lpr);
-  if (st != MREC_OK) return st;
-  ApplyArgs a{};
-  st = lg_apply_args(bank, ba, dx, dx_dtype, dx_ld, dfm, fm_sum, x0, x0_dtype, x0_ld, dw, mode,
-                     lr, seed, d_step, grad, &a);
-  if (st != MREC_OK) return st;
-  return lg_fused_impl(bank, ids, batch, workspace, ws_bytes, d_oob_flag, a, n_reduce, reduce,
-                       stream);
+  BwdRequest r;
+  r.who = __func__;
+  r.dx = dx, r.dx_dtype = dx_dtype, r.dx_ld = dx_ld, r.dfm = dfm, r.fm_sum = fm_sum;
+  r.x0 = x0, r.x0_dtype = x0_dtype, r.x0_ld = x0_ld, r.dw = dw;
+  r.mode = mode, r.lr = lr, r.seed = seed, r.d_step = d_step, r.grad = grad;
+  r.n_reduce = n_reduce, r.reduce = reduce;
+  return lg_fused_request(bank, ids, batch, workspace, ws_bytes, d_oob_flag, stream, r);
 }
 
 mrec_status mrec_emb_bwd_large_fused_bag(const mrec_table_bank *bank, const mrec_ids *ids,
@@ -1667,24 +1614,14 @@ mrec_status mrec_emb_bwd_large_fused_bag(const mrec_table_bank *bank, const mrec
                                          int32_t n_reduce, const mrec_gemm_call *reduce,
                                          mrec_stream stream, int32_t bag_len,
                                          const float *bag_scale) {
-  MREC_CHECK_ARG(bank != nullptr, "NULL bank");
-  MREC_CHECK_ARG(bag_len >= 1, "bag_len < 1");
-  MREC_CHECK_ARG(batch >= 0 && batch % bag_len == 0, "batch is not a multiple of bag_len");
-  MREC_CHECK_ARG(bag_scale != nullptr, "bag_scale is NULL");
-  MREC_CHECK_ARG(dfm == nullptr, "the FM term is undefined for bags (dfm must be NULL)");
-  BankArgs ba;
-  int es = 0, lpr = 0;
-  mrec_status st = make_bank_args(bank, &ba, &es, &lpr);
-  if (st != MREC_OK) return st;
-  ApplyArgs a{};
-  st = lg_apply_args(bank, ba, dx, dx_dtype, dx_ld, dfm, fm_sum, x0, x0_dtype, x0_ld, dw, mode,
-                     lr, seed, d_step, grad, &a);
-  if (st != MREC_OK) return st;
-  a.bag = bag_len;  // (dx / dw hold batch / bag_len rows: one per bag)
-  a.bag_scale = bag_scale;
-  a.g_F = ba.n_tables;
-  return lg_fused_impl(bank, ids, batch, workspace, ws_bytes, d_oob_flag, a, n_reduce, reduce,
-                       stream);
+  BwdRequest r;
+  r.who = __func__;
+  r.dx = dx, r.dx_dtype = dx_dtype, r.dx_ld = dx_ld, r.dfm = dfm, r.fm_sum = fm_sum;
+  r.x0 = x0, r.x0_dtype = x0_dtype, r.x0_ld = x0_ld, r.dw = dw;
+  r.mode = mode, r.lr = lr, r.seed = seed, r.d_step = d_step, r.grad = grad;
+  r.n_reduce = n_reduce, r.reduce = reduce;
+  r.bag = true, r.bag_len = bag_len, r.bag_scale = bag_scale;
+  return lg_fused_request(bank, ids, batch, workspace, ws_bytes, d_oob_flag, stream, r);
 }
 
 mrec_status mrec_emb_bwd_large_fused_given(const mrec_table_bank *bank, const mrec_ids *ids,
@@ -1693,45 +1630,15 @@ mrec_status mrec_emb_bwd_large_fused_given(const mrec_table_bank *bank, const mr
                                            mrec_bwd_mode mode, float lr, uint64_t seed,
                                            const uint64_t *d_step, void *grad, int32_t n_reduce,
                                            const mrec_gemm_call *reduce, mrec_stream stream) {
-  MREC_CHECK_ARG(bank != nullptr && given != nullptr, "NULL bank / given");
-  const mrec_given_grads &g = *given;
-  MREC_CHECK_ARG((g.g_occ != nullptr) != (g.wire != nullptr), "exactly one of g_occ / wire");
-  MREC_CHECK_ARG(g.chunk >= 1, "chunk (entries per exchange part) must be >= 1");
-  BankArgs ba;
-  int es = 0, lpr = 0;
-  mrec_status st = make_bank_args(bank, &ba, &es, &lpr);
-  if (st != MREC_OK) return st;
-  ApplyArgs a{};
-  st = lg_apply_args(bank, ba, nullptr, MREC_F32, 0, nullptr, nullptr, nullptr, MREC_F32, 0,
-                     nullptr, mode, lr, seed, d_step, grad, &a);
-  if (st != MREC_OK) return st;
-  a.chunk = g.chunk;
-  if (g.g_occ) {
-    MREC_CHECK_ARG(g.g_ld >= ba.dim + (ba.has_w ? 1 : 0) && g.g_ld % 4 == 0 &&
-                       (reinterpret_cast<uintptr_t>(g.g_occ) & 15) == 0,
-                   "g_occ rows: >= dim (+w) floats, 16-B aligned");
-    MREC_CHECK_ARG(g.chunk_stride >= static_cast<int64_t>(ba.n_tables) * g.chunk,
-                   "chunk_stride < n_tables * chunk");
-    a.g_occ = g.g_occ;
-    a.g_ld = g.g_ld;
-    a.chunk_stride = g.chunk_stride;
-  } else {
-    MREC_CHECK_ARG(g.wire_dtype == MREC_BF16 || g.wire_dtype == MREC_F32,
-                   "wire dtype must be BF16/F32");
-    const int wes = g.wire_dtype == MREC_BF16 ? 2 : 4;
-    MREC_CHECK_ARG(g.rec_bytes > 0 && g.rec_bytes % wes == 0 && g.rec_bytes % 4 == 0 &&
-                       g.rec_bytes >= (ba.dim + (ba.has_w ? 1 : 0)) * wes,
-                   "bad record bytes");
-    MREC_CHECK_ARG(g.pref != nullptr && g.cap_rows >= 1, "NULL pref / cap_rows < 1");
-    a.g_rec = g.wire;
-    a.g_rec_bf16 = g.wire_dtype == MREC_BF16;
-    a.g_rec_pitch = g.rec_bytes / wes;
-    a.g_pref = g.pref;
-    a.g_cap_rows = g.cap_rows;
-  }
-  a.g_F = ba.n_tables;
-  return lg_fused_impl(bank, ids, batch, workspace, ws_bytes, d_oob_flag, a, n_reduce, reduce,
-                       stream);
+  MREC_CHECK_ARG(given != nullptr, "NULL given");
+  MREC_CHECK_ARG((given->g_occ != nullptr) != (given->wire != nullptr),
+                 "exactly one of g_occ / wire");
+  BwdRequest r;
+  r.who = __func__;
+  r.set_given(*given);
+  r.mode = mode, r.lr = lr, r.seed = seed, r.d_step = d_step, r.grad = grad;
+  r.n_reduce = n_reduce, r.reduce = reduce;
+  return lg_fused_request(bank, ids, batch, workspace, ws_bytes, d_oob_flag, stream, r);
 }
 
 mrec_status mrec_emb_bwd_large_fused(const mrec_table_bank *bank, const mrec_ids *ids,
@@ -1741,37 +1648,20 @@ mrec_status mrec_emb_bwd_large_fused(const mrec_table_bank *bank, const mrec_ids
                                      const void *x0, mrec_dtype x0_dtype, int64_t x0_ld,
                                      const float *dw, mrec_bwd_mode mode, float lr, uint64_t seed,
                                      const uint64_t *d_step, void *grad, mrec_stream stream) {
-  return mrec_emb_bwd_large_fused_ex(bank, ids, batch, workspace, ws_bytes, d_oob_flag, dx,
-                                     dx_dtype, dx_ld, dfm, fm_sum, x0, x0_dtype, x0_ld, dw, mode,
-                                     lr, seed, d_step, grad, 0, nullptr, stream);
+  BwdRequest r;
+  r.who = __func__;
+  r.dx = dx, r.dx_dtype = dx_dtype, r.dx_ld = dx_ld, r.dfm = dfm, r.fm_sum = fm_sum;
+  r.x0 = x0, r.x0_dtype = x0_dtype, r.x0_ld = x0_ld, r.dw = dw;
+  r.mode = mode, r.lr = lr, r.seed = seed, r.d_step = d_step, r.grad = grad;
+  return lg_fused_request(bank, ids, batch, workspace, ws_bytes, d_oob_flag, stream, r);
 }
 
 }  // extern "C"
 
 // mrec_emb_bwd_large_fused_bag's kernels.  Dispatched last in the file, so the code
 // object lays the other kernels out as it would without them.
-static void lg_dispatch_apply_bag(mrec_dtype dtype, int lpr, const BankArgs &ba, int64_t batch,
-                                  const LgWs &w, const ApplyArgs &a, int stride, int fused_nb,
-                                  int G, int lognb, hipStream_t s, const CoReduce &co,
-                                  int co_blocks) {
-#define MREC_LGB(T, L) \
-  lg_launch_apply<T, L, true>(ba, batch, w, a, stride, fused_nb, G, lognb, co, co_blocks, s)
-  if (dtype == MREC_BF16) {
-    switch (lpr) {
-      case 1: MREC_LGB(uint16_t, 1); break;
-      case 2: MREC_LGB(uint16_t, 2); break;
-      case 4: MREC_LGB(uint16_t, 4); break;
-      case 8: MREC_LGB(uint16_t, 8); break;
-      default: MREC_LGB(uint16_t, 16); break;
-    }
-  } else {
-    switch (lpr) {
-      case 1: MREC_LGB(float, 1); break;
-      case 2: MREC_LGB(float, 2); break;
-      case 4: MREC_LGB(float, 4); break;
-      case 8: MREC_LGB(float, 8); break;
-      default: MREC_LGB(float, 16); break;
-    }
-  }
-#undef MREC_LGB
+static void lg_dispatch_apply_bag(mrec_dtype dtype, int lpr, const LgLaunch &x) {
+  for_row_geometry(dtype, lpr, [&](auto t, auto l) {
+    lg_launch_apply<decltype(t), decltype(l)::value, true>(x);
+  });
 }

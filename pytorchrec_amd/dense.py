@@ -289,6 +289,15 @@ def take_pending(n: int):
     return jobs
 
 
+def co_reduce_args():
+    """Up to CO_REDUCE_MAX deferred reductions as the ``n_reduce, reduce`` arguments of a
+    launch that runs them beside its own work -> (n, GemmCall array or None, keep-alive).
+    The array points into the keep-alive: hold it until ``_mrec.call`` has returned."""
+    jobs = take_pending(CO_REDUCE_MAX)
+    arr = (_mrec.GemmCall * len(jobs))(*[j.struct() for j in jobs]) if jobs else None
+    return len(jobs), arr, jobs
+
+
 def _defer(call: "_Call"):
     _PENDING.append(call.with_phase(_mrec.GEMM_REDUCE))
     torch.autograd.Variable._execution_engine.queue_callback(flush_pending)

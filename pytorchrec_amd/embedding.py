@@ -360,24 +360,23 @@ def _apply(bank: EmbeddingBank, ws, ws_bytes, count, dx=None, dfm=None, fm_sum=N
     """Run the fused backward for lookups [0, count) described by ``ws``; the
     per-sample tensors must already be sliced to the same chunk.  ``bag`` = (L, scale):
     the lookups are the positions of count / L pooled bags (mrec_emb_bwd_apply_bag)."""
-    mode, lr = bank.apply_mode()
-    dx_dt = _mrec.dtype_code(dx.dtype) if dx is not None else _mrec.F32
-    x0_dt = _mrec.dtype_code(x0.dtype) if x0 is not None else _mrec.F32
     # deferred MLP weight-gradient reductions (+ fused SGD) ride along this launch
     from pytorchrec_amd import dense as dense_ops
-    jobs = dense_ops.take_pending(dense_ops.CO_REDUCE_MAX)
-    arr = (_mrec.GemmCall * len(jobs))(*[j.struct() for j in jobs]) if jobs else None
+    n_co, co, keep = dense_ops.co_reduce_args()
     args = (bank.desc().ref(), count, ws.data_ptr(), ws_bytes,
-            _mrec.ptr(dx), dx_dt, dx.stride(0) if dx is not None else 0,
-            _mrec.ptr(dfm), _mrec.ptr(fm_sum), _mrec.ptr(x0), x0_dt,
-            x0.stride(0) if x0 is not None else 0, _mrec.ptr(dw), mode, float(lr),
-            bank.next_seed(), bank.step_counter().data_ptr(), _mrec.ptr(grad), len(jobs),
-            arr, _mrec.stream_handle())
+            *_mrec.grad_source(dx, dfm, fm_sum, x0, dw), *_update_args(bank, grad), n_co, co,
+            _mrec.stream_handle())
     if bag is None:
         _mrec.call("mrec_emb_bwd_apply_ex", *args)
     else:
         _mrec.call("mrec_emb_bwd_apply_bag", *args, int(bag[0]), bag[1].data_ptr())
-    del jobs
+    del keep
+
+
+def _update_args(bank: EmbeddingBank, grad):
+    """The update arguments of an apply on the bank's own rows: mode, lr, seed, d_step, grad."""
+    mode, lr = bank.apply_mode()
+    return (mode, float(lr), bank.next_seed(), bank.step_counter().data_ptr(), _mrec.ptr(grad))
 
 
 def _chunks(batch: int):
@@ -410,38 +409,25 @@ def _backward_large(bank: EmbeddingBank, ids, batch, grad, dx=None, dfm=None, fm
     (mrec_emb_bwd_large_fused: the bucketed plan with the updates in the bucket
     kernel; the plan / apply pair when the batch is too large for it)."""
     ws = _large_ws(bank, batch)
-    mode, lr = bank.apply_mode()
+    src = _mrec.grad_source(dx, dfm, fm_sum, x0, dw)
     if not LARGE_FUSED and bag is None:
         _mrec.call("mrec_emb_bwd_large_plan", bank.desc().ref(), _ids_desc(ids).ref(), batch,
                    ws.data_ptr(), ws.numel(), None, _mrec.stream_handle())
         _mrec.call("mrec_emb_bwd_large_apply", bank.desc().ref(), batch, ws.data_ptr(),
-                   ws.numel(), *_large_apply_args(bank, grad, dx, dfm, fm_sum, x0, dw, mode, lr))
+                   ws.numel(), *src, *_update_args(bank, grad), _mrec.stream_handle())
         return
     # deferred MLP weight-gradient reductions (DIN's top tower) ride along the bucket kernel
     from pytorchrec_amd import dense as dense_ops
-    jobs = dense_ops.take_pending(dense_ops.CO_REDUCE_MAX)
-    arr = (_mrec.GemmCall * len(jobs))(*[j.struct() for j in jobs]) if jobs else None
-    args = _large_apply_args(bank, grad, dx, dfm, fm_sum, x0, dw, mode, lr)
+    n_co, co, keep = dense_ops.co_reduce_args()
+    args = (bank.desc().ref(), _ids_desc(ids).ref(), batch, ws.data_ptr(), ws.numel(), None,
+            *src, *_update_args(bank, grad), n_co, co, _mrec.stream_handle())
     if bag is None:
-        _mrec.call("mrec_emb_bwd_large_fused_ex", bank.desc().ref(), _ids_desc(ids).ref(), batch,
-                   ws.data_ptr(), ws.numel(), None, *args[:-1], len(jobs), arr, args[-1])
+        _mrec.call("mrec_emb_bwd_large_fused_ex", *args)
     else:  # the lookups are the positions of batch / L pooled bags
-        _mrec.call("mrec_emb_bwd_large_fused_bag", bank.desc().ref(), _ids_desc(ids).ref(), batch,
-                   ws.data_ptr(), ws.numel(), None, *args[:-1], len(jobs), arr, args[-1],
-                   int(bag[0]), bag[1].data_ptr())
-    del jobs
+        _mrec.call("mrec_emb_bwd_large_fused_bag", *args, int(bag[0]), bag[1].data_ptr())
+    del keep
     if bank.check_ids and not torch.cuda.is_current_stream_capturing():
         bank.check_flags()
-
-
-def _large_apply_args(bank, grad, dx, dfm, fm_sum, x0, dw, mode, lr):
-    """The apply arguments of mrec_emb_bwd_large_apply / _fused after the workspace."""
-    return (_mrec.ptr(dx), _mrec.dtype_code(dx.dtype) if dx is not None else _mrec.F32,
-            dx.stride(0) if dx is not None else 0, _mrec.ptr(dfm), _mrec.ptr(fm_sum),
-            _mrec.ptr(x0), _mrec.dtype_code(x0.dtype) if x0 is not None else _mrec.F32,
-            x0.stride(0) if x0 is not None else 0, _mrec.ptr(dw), mode, float(lr),
-            bank.next_seed(), bank.step_counter().data_ptr(), _mrec.ptr(grad),
-            _mrec.stream_handle())
 
 
 def _backward_into_bank(bank: EmbeddingBank, ids, batch, plan_ws, dx=None, dfm=None,

@@ -643,16 +643,12 @@ def sender_grad_sums(bank: ShardedEmbeddingBank, rows_recv: torch.Tensor, pos: t
     ws, wsb = plan
     B = pos.shape[1]
     from pytorchrec_amd import dense as dense_ops
-    jobs = dense_ops.take_pending(dense_ops.CO_REDUCE_MAX)
-    arr = (_mrec.GemmCall * len(jobs))(*[j.struct() for j in jobs]) if jobs else None
+    n_co, co, keep = dense_ops.co_reduce_args()
     rdesc = remote_desc(bank, rows_recv)
     _mrec.call("mrec_emb_bwd_apply_ex", rdesc.ref(), B, ws.data_ptr(), wsb,
-               _mrec.ptr(dx), _mrec.dtype_code(dx.dtype) if dx is not None else _mrec.F32,
-               dx.stride(0) if dx is not None else 0, _mrec.ptr(dfm), _mrec.ptr(fm_sum),
-               _mrec.ptr(x0), _mrec.dtype_code(x0.dtype) if x0 is not None else _mrec.F32,
-               x0.stride(0) if x0 is not None else 0, _mrec.ptr(dw), _mrec.BWD_DENSE_GRAD, 0.0,
-               0, None, gsum.data_ptr(), len(jobs), arr, _mrec.stream_handle())
-    del jobs
+               *_mrec.grad_source(dx, dfm, fm_sum, x0, dw), _mrec.BWD_DENSE_GRAD, 0.0, 0, None,
+               gsum.data_ptr(), n_co, co, _mrec.stream_handle())
+    del keep
     return gsum
 
 
@@ -670,16 +666,12 @@ def sender_grad_records(bank: ShardedEmbeddingBank, rows_recv: torch.Tensor, pos
     wire = torch.empty(P, bank.cap_rows * rb, dtype=torch.uint8, device=bank.weight.device)
     out = _mrec.GradRecords(wire.data_ptr(), rb, spref.data_ptr(), bank.cap, bank.cap_rows)
     from pytorchrec_amd import dense as dense_ops
-    jobs = dense_ops.take_pending(dense_ops.CO_REDUCE_MAX)
-    arr = (_mrec.GemmCall * len(jobs))(*[j.struct() for j in jobs]) if jobs else None
+    n_co, co, keep = dense_ops.co_reduce_args()
     rdesc = remote_desc(bank, rows_recv)
     _mrec.call("mrec_emb_bwd_apply_rec", rdesc.ref(), B, ws.data_ptr(), wsb,
-               _mrec.ptr(dx), _mrec.dtype_code(dx.dtype) if dx is not None else _mrec.F32,
-               dx.stride(0) if dx is not None else 0, _mrec.ptr(dfm), _mrec.ptr(fm_sum),
-               _mrec.ptr(x0), _mrec.dtype_code(x0.dtype) if x0 is not None else _mrec.F32,
-               x0.stride(0) if x0 is not None else 0, _mrec.ptr(dw), ctypes.byref(out),
-               len(jobs), arr, _mrec.stream_handle())
-    del jobs
+               *_mrec.grad_source(dx, dfm, fm_sum, x0, dw), ctypes.byref(out), n_co, co,
+               _mrec.stream_handle())
+    del keep
     return wire
 
 
@@ -769,10 +761,7 @@ def shard_lookup_grad(bank: ShardedEmbeddingBank, pos: torch.Tensor, batch: int,
     F, W, cap = bank.n_tables, bank.world, bank.cap
     g = torch.empty(W * F * cap, bank.g_ld, dtype=torch.float32, device=bank.weight.device)
     _mrec.call("mrec_shard_lookup_grad", batch, F, bank.dim, int(bank.has_w), pos.data_ptr(),
-               _mrec.ptr(dx), _mrec.dtype_code(dx.dtype) if dx is not None else _mrec.F32,
-               dx.stride(0) if dx is not None else 0, _mrec.ptr(dfm), _mrec.ptr(fm_sum),
-               _mrec.ptr(x0), _mrec.dtype_code(x0.dtype) if x0 is not None else _mrec.F32,
-               x0.stride(0) if x0 is not None else 0, _mrec.ptr(dw), g.data_ptr(), g.shape[1],
+               *_mrec.grad_source(dx, dfm, fm_sum, x0, dw), g.data_ptr(), g.shape[1],
                _mrec.stream_handle())
     return g
 
@@ -786,25 +775,15 @@ def owner_apply(bank: ShardedEmbeddingBank, plan, g_recv: torch.Tensor,
     explicit ``lr`` runs plain SGD with exactly that step (kernel tests)."""
     ws, wsb = plan
     F, W, cap = bank.n_tables, bank.world, bank.cap
-    if grad is not None:  # the summed gradient into a dense buffer (kernel tests)
-        mode, lr = _mrec.BWD_DENSE_GRAD, 0.0
-    elif lr is not None:
-        mode = (_mrec.BWD_SGD_SR if (bank.stochastic_rounding and
-                                     bank.weight.dtype == torch.bfloat16) else _mrec.BWD_SGD)
-    else:
-        mode, lr = bank.apply_mode()
-        if mode in (_mrec.BWD_SGD, _mrec.BWD_SGD_SR):
-            lr = lr / W
+    mode, lr = _owner_mode(bank, lr, grad)
     # deferred MLP weight-gradient reductions ride along this launch
     from pytorchrec_amd import dense as dense_ops
-    jobs = dense_ops.take_pending(dense_ops.CO_REDUCE_MAX)
-    arr = (_mrec.GemmCall * len(jobs))(*[j.struct() for j in jobs]) if jobs else None
+    n_co, co, keep = dense_ops.co_reduce_args()
     _mrec.call("mrec_emb_bwd_apply_given", bank.desc().ref(), W * cap, ws.data_ptr(), wsb,
-               None, _mrec.F32, 0, None, None, None, _mrec.F32, 0, None, g_recv.data_ptr(),
+               *_mrec.grad_source(None, None, None, None, None), g_recv.data_ptr(),
                g_recv.shape[1], cap, F * cap, mode, float(lr), bank.next_seed(),
-               bank.step_counter().data_ptr(), _mrec.ptr(grad), len(jobs), arr,
-               _mrec.stream_handle())
-    del jobs
+               bank.step_counter().data_ptr(), _mrec.ptr(grad), n_co, co, _mrec.stream_handle())
+    del keep
 
 
 def owner_apply_wire(bank: ShardedEmbeddingBank, plan, wire_g: torch.Tensor, pref: torch.Tensor,
@@ -818,21 +797,21 @@ def owner_apply_wire(bank: ShardedEmbeddingBank, plan, wire_g: torch.Tensor, pre
     F, W, cap = bank.n_tables, parts or bank.world, bank.cap
     mode, lr = _owner_mode(bank, lr, grad)
     from pytorchrec_amd import dense as dense_ops
-    jobs = dense_ops.take_pending(dense_ops.CO_REDUCE_MAX)
-    arr = (_mrec.GemmCall * len(jobs))(*[j.struct() for j in jobs]) if jobs else None
+    n_co, co, keep = dense_ops.co_reduce_args()
     args = (bank.desc().ref(), W * cap, ws.data_ptr(), wsb, wire_g.data_ptr(), bank.wire_bytes(),
             _mrec.dtype_code(bank.weight.dtype), pref.data_ptr(), bank.cap_rows, cap, F * cap, mode,
             float(lr), bank.next_seed(), bank.step_counter().data_ptr(), _mrec.ptr(grad),
-            len(jobs), arr)
+            n_co, co)
     if sgd is not None:
         _mrec.call("mrec_emb_bwd_apply_wire_sgd", *args, sgd[0].data_ptr(), int(sgd[1]),
                    _mrec.stream_handle())
     else:
         _mrec.call("mrec_emb_bwd_apply_wire", *args, _mrec.stream_handle())
-    del jobs
+    del keep
 
 
 def _owner_mode(bank: ShardedEmbeddingBank, lr, grad):
+    """(mode, lr) of an owner-side apply, as owner_apply describes them."""
     if grad is not None:
         return _mrec.BWD_DENSE_GRAD, 0.0
     if lr is not None:
@@ -877,14 +856,13 @@ def owner_apply_large(bank: ShardedEmbeddingBank, recv_ids: torch.Tensor, part: 
         g.wire_dtype, g.pref, g.cap_rows = (_mrec.dtype_code(bank.weight.dtype), pref.data_ptr(),
                                             bank.cap_rows)
     from pytorchrec_amd import dense as dense_ops
-    jobs = dense_ops.take_pending(dense_ops.CO_REDUCE_MAX)
-    arr = (_mrec.GemmCall * len(jobs))(*[j.struct() for j in jobs]) if jobs else None
+    n_co, co, keep = dense_ops.co_reduce_args()
     fl = bank.flags()
     _mrec.call("mrec_emb_bwd_large_fused_given", bank.desc().ref(), idd.ref(), n, ws.data_ptr(),
                ws.numel(), fl.data_ptr() + 4, ctypes.byref(g), mode, float(lr), bank.next_seed(),
-               bank.step_counter().data_ptr(), _mrec.ptr(grad), len(jobs), arr,
+               bank.step_counter().data_ptr(), _mrec.ptr(grad), n_co, co,
                _mrec.stream_handle())
-    del jobs
+    del keep
 
 
 def _large_ws_for(bank: ShardedEmbeddingBank, n: int) -> torch.Tensor:
