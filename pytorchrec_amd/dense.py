@@ -20,7 +20,7 @@ row starts 16-byte aligned.
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 import torch.nn.functional as F
@@ -84,6 +84,24 @@ def _is_relu_out(x: torch.Tensor) -> bool:
     return getattr(x, _RELU_OUT, False) and x.is_cuda
 
 
+# the tensors of an mrec_epilogue -> the field that takes a matrix's row stride
+_EPI_LD = {"bias": None, "ones_out": None, "mul": "ld_mul", "add": "ld_add", "aux": "ld_aux",
+           "mask": "ld_mask", "img_row": "ld_img_row", "img_tr": "ld_img_tr"}
+
+
+def _epilogue(act=0, sgd_lr=None, img_kind=0, **tensors) -> _mrec.Epilogue:
+    """mrec_epilogue by field name; ``tensors``: any of _EPI_LD, each may be None."""
+    e = _mrec.Epilogue(act=act, update=int(sgd_lr is not None),
+                       lr=float(sgd_lr) if sgd_lr is not None else 0.0, img_kind=img_kind)
+    for name, t in tensors.items():
+        ld = _EPI_LD[name]
+        if t is not None:
+            setattr(e, name, t.data_ptr())
+            if ld:
+                setattr(e, ld, t.stride(0))
+    return e
+
+
 def gemm(A, a_layout, B, b_layout, M, N, K, *, ones_out=None, b_cols=None, bias=None, act=0,
          mul=None, add=None, aux=None, mask=None, out=None, out_dtype=_BF16, split_k=None,
          sgd_lr=None, img_row=None, img_tr=None, img_kind=0):
@@ -97,15 +115,8 @@ def gemm(A, a_layout, B, b_layout, M, N, K, *, ones_out=None, b_cols=None, bias=
         split_k = _split_for(M, N + (ones_out is not None), K)
     ws_bytes = _mrec.lib().mrec_gemm_workspace_size(M, N, K, split_k)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-    epi = _mrec.Epilogue(_mrec.ptr(bias), act, _mrec.ptr(mul), mul.stride(0) if mul is not None else 0,
-                         _mrec.ptr(add), add.stride(0) if add is not None else 0,
-                         _mrec.ptr(aux), aux.stride(0) if aux is not None else 0,
-                         _mrec.ptr(mask), mask.stride(0) if mask is not None else 0,
-                         _mrec.ptr(ones_out), int(sgd_lr is not None),
-                         float(sgd_lr) if sgd_lr is not None else 0.0,
-                         _mrec.ptr(img_row), img_row.stride(0) if img_row is not None else 0,
-                         _mrec.ptr(img_tr), img_tr.stride(0) if img_tr is not None else 0,
-                         img_kind)
+    epi = _epilogue(act, sgd_lr, img_kind, bias=bias, mul=mul, add=add, aux=aux, mask=mask,
+                    ones_out=ones_out, img_row=img_row, img_tr=img_tr)
     a_op, b_op = _op(A, a_layout), _op(B, b_layout)
     _mrec.call("mrec_gemm", M, N, K, ctypes.byref(a_op), ctypes.byref(b_op),
                N if ones_out is not None else -1, N if b_cols is None else b_cols,
@@ -129,19 +140,13 @@ class _Call:
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         self.out, self.ws = out, ws
         self.keep = [A, B, ones_out, mask, img_row, img_tr, out, ws, add]
-        self.epi = _mrec.Epilogue(None, 0, None, 0,
-                                  _mrec.ptr(add), add.stride(0) if add is not None else 0, None, 0,
-                                  _mrec.ptr(mask), mask.stride(0) if mask is not None else 0,
-                                  _mrec.ptr(ones_out), int(sgd_lr is not None),
-                                  float(sgd_lr) if sgd_lr is not None else 0.0,
-                                  _mrec.ptr(img_row), img_row.stride(0) if img_row is not None else 0,
-                                  _mrec.ptr(img_tr), img_tr.stride(0) if img_tr is not None else 0,
-                                  img_kind)
+        self.epi = _epilogue(_mrec.ACT_NONE, sgd_lr, img_kind, add=add, mask=mask,
+                             ones_out=ones_out, img_row=img_row, img_tr=img_tr)
         self.a, self.b = _op(A, a_layout), _op(B, b_layout)
         self.args = (M, N, K, N if ones_out is not None else -1, N if b_cols is None else b_cols,
                      out.data_ptr(), _mrec.dtype_code(out.dtype), out.stride(0), split_k,
                      _mrec.ptr(ws), ws_bytes)
-        self.phase = phase
+        self.phase, self.split_k = phase, split_k
         self.writes = {p for p in (out.data_ptr(), _mrec.ptr(ones_out), _mrec.ptr(img_row),
                                    _mrec.ptr(img_tr)) if p}
         self.reads = {A.data_ptr(), B.data_ptr()} | ({add.data_ptr()} if add is not None else set())
@@ -158,40 +163,22 @@ class _Call:
                               ctypes.pointer(self.epi), C, cdt, ldc, sk, ws, wsb, self.phase)
 
 
-_PENDING = []  # deferred split-K reductions (fused SGD of a layer's W, b and images)
-CO_REDUCE_MAX = 6  # reductions one embedding-update launch takes along (gemm_common.h kMaxCoReduce)
-
-# measurement hook (bench.py): when a dict, the tower launches of eager steps are
-# bracketed by HIP events on their stream: {name: [(start, end), ...]}
-KERNEL_EVENTS = None
-
-
-class _timed:
-    def __init__(self, name):
-        self.name = name
-
-    def __enter__(self):
-        if KERNEL_EVENTS is not None:
-            # keep the queue busy (~80 us spin) so the start event and the launch are
-            # both queued when the GPU reaches them: the host's launch latency of an
-            # eager step is then outside the bracket
-            torch.cuda._sleep(200000)
-            self.e0 = torch.cuda.Event(enable_timing=True)
-            self.e0.record()
-        return self
-
-    def __exit__(self, *exc):
-        if KERNEL_EVENTS is not None:
-            e1 = torch.cuda.Event(enable_timing=True)
-            e1.record()
-            KERNEL_EVENTS.setdefault(self.name, []).append((self.e0, e1))
-        return False
-
-
-# the batch feed's copy of a later batch (an mrec_feed_job, loader.capture_steps),
-# taken by the next mrec_tower_dw launch: its PCIe reads then run in extra workgroups
-# beside the L2-bound weight-gradient tiles instead of on the step's critical path
+# ----------------------------------------------------------------------------
+# deferred work: three module-level lists, only ever mutated in place
+# ----------------------------------------------------------------------------
+# _PENDING: split-K REDUCE jobs (a layer's dW reduction with its fused SGD or flat DP
+#   write) that wait for a later launch to take them along: launch_multi, the
+#   tower's dW launch, the embedding update (co_reduce_args); flush_pending at the
+#   end of the backward runs whatever is left.
+# _FINISH: at most one deferred CTR head finish, taken by the next GEMM launch.
+# _FEED_JOB: the batch feed's copy of a later batch (an mrec_feed_job,
+#   loader.capture_steps), taken by the next mrec_tower_dw launch: its PCIe reads
+#   then run in extra workgroups beside the L2-bound weight-gradient tiles instead
+#   of on the step's critical path.
+_PENDING = []
+_FINISH = []
 _FEED_JOB = []
+CO_REDUCE_MAX = 6  # reductions one embedding-update launch takes along (gemm_common.h kMaxCoReduce)
 
 
 def set_feed_job(job):
@@ -204,47 +191,80 @@ def take_feed_job():
     return job
 
 
-def launch_multi(calls):
-    """Run ``calls`` plus the pending deferred reductions in as few launches as
-    possible (<= 4 problems each; a pending job that writes what a call reads is
-    flushed first)."""
-    global _PENDING
-    pend = _PENDING
-    reads = set().union(*[c.reads for c in calls]) if calls else set()
-    if any(p.writes & reads for p in pend):
-        _run(pend)
-        pend = []
-    jobs = list(calls) + pend
-    _PENDING = []
+def take_pending(n: int):
+    """Remove and return up to ``n`` deferred reductions, for a launch that runs
+    them beside its own work (``mrec_emb_bwd_apply_ex``)."""
+    jobs = _PENDING[:n]
+    del _PENDING[:n]
+    return jobs
+
+
+def co_reduce_args():
+    """Up to CO_REDUCE_MAX deferred reductions as the ``n_reduce, reduce`` arguments of a
+    launch that runs them beside its own work -> (n, GemmCall array or None, keep-alive).
+    The array points into the keep-alive: hold it until ``_mrec.call`` has returned."""
+    jobs = take_pending(CO_REDUCE_MAX)
+    arr = (_mrec.GemmCall * len(jobs))(*[j.struct() for j in jobs]) if jobs else None
+    return len(jobs), arr, jobs
+
+
+def _take_finish():
+    """The deferred head finish for the launch about to be made, or None."""
+    return _FINISH.pop(0) if _FINISH else None
+
+
+def _run(jobs):
+    if not jobs:
+        return
+    arr = (_mrec.GemmCall * len(jobs))(*[j.struct() for j in jobs])
+    fin = _take_finish()
+    if fin is None:
+        _mrec.call("mrec_gemm_multi", len(jobs), arr, _mrec.stream_handle())
+        return
+    _mrec.call("mrec_gemm_multi_ex", len(jobs), arr, None, ctypes.byref(fin.struct),
+               _mrec.stream_handle())
+
+
+def _run_all(jobs):
+    """``jobs`` in launches of at most four problems (mrec_gemm_multi's limit)."""
     for i in range(0, len(jobs), 4):
         _run(jobs[i:i + 4])
 
 
-class _HeadFinish:
-    """A deferred mrec_ctr_head_finish in SGD-update mode (the head's W, b and side
-    linear ws, b2): run by spare workgroups of the next GEMM launch, or on its own
-    at the end of the backward."""
+def _flush_writers(reads):
+    """A launch is about to read the addresses ``reads``: if a pending job writes one
+    of them, every pending job runs first, in launches of their own."""
+    if any(p.writes & reads for p in _PENDING):
+        _run_all(take_pending(len(_PENDING)))
 
-    def __init__(self, part, B, H, ns, g, lr, w, bias, ws, b2, grads=None):
-        self.keep = [part, g, w, bias, ws, b2, grads]
-        if grads is None:  # SGD update in place
-            self.struct = _mrec.HeadFinishJob(part.data_ptr(), part.stride(0), B, H, ns,
-                                              _mrec.ptr(g), 1, float(lr), w.data_ptr(),
-                                              _mrec.ptr(bias), _mrec.ptr(ws), _mrec.ptr(b2),
-                                              None, None, None, None)
-        else:  # gradients into the data-parallel flat buffer views
-            self.struct = _mrec.HeadFinishJob(part.data_ptr(), part.stride(0), B, H, ns,
-                                              _mrec.ptr(g), 0, 0.0, None, None, None, None,
-                                              *[_mrec.ptr(t) for t in grads])
+
+def launch_multi(calls):
+    """Run ``calls`` plus the pending deferred reductions in as few launches as
+    possible (a pending job that writes what a call reads is flushed first)."""
+    _flush_writers(set().union(*[c.reads for c in calls]))
+    _run_all(list(calls) + take_pending(len(_PENDING)))
+
+
+class _HeadFinish:
+    """One mrec_ctr_head_finish over the head's (w, b, ws, b2): the SGD update in place
+    (``lr``, ``params``) or the gradients into ``grads``.  Deferred
+    (``defer_head_finish``) it is run by spare workgroups of the next GEMM launch, or
+    on its own at the end of the backward."""
+
+    def __init__(self, part, B, H, ns, g, lr=None, params=None, grads=None):
+        update = grads is None
+        self.keep = [part, g, params, grads]
+        ptrs = [_mrec.ptr(t) for t in (params if update else grads)]
+        none = [None] * 4
+        self.struct = _mrec.HeadFinishJob(part.data_ptr(), part.stride(0), B, H, ns, _mrec.ptr(g),
+                                          int(update), float(lr) if update else 0.0,
+                                          *(ptrs + none if update else none + ptrs))
 
     def run(self):
         j = self.struct
         _mrec.call("mrec_ctr_head_finish", j.part, j.ldp, j.batch, j.H, j.ns, j.g, j.update, j.lr,
                    j.w, j.bias, j.ws, j.b2, j.dw_out, j.db_out, j.dws_out, j.db2_out,
                    _mrec.stream_handle())
-
-
-_FINISH = []
 
 
 def defer_head_finish(fin: _HeadFinish):
@@ -258,44 +278,12 @@ def _flush_finish():
         _FINISH.pop(0).run()
 
 
-def _run(jobs):
-    if not jobs:
-        return
-    arr = (_mrec.GemmCall * len(jobs))(*[j.struct() for j in jobs])
-    fin = _FINISH.pop(0) if _FINISH else None
-    if fin is None:
-        _mrec.call("mrec_gemm_multi", len(jobs), arr, _mrec.stream_handle())
-        return
-    _mrec.call("mrec_gemm_multi_ex", len(jobs), arr, None, ctypes.byref(fin.struct),
-               _mrec.stream_handle())
-
-
 def flush_pending():
     """Apply every deferred reduction now (queued as an autograd end-of-backward
     callback whenever one is deferred, so a backward pass never ends with work
     pending)."""
-    global _PENDING
-    pend, _PENDING = _PENDING, []
-    for i in range(0, len(pend), 4):
-        _run(pend[i:i + 4])
+    _run_all(take_pending(len(_PENDING)))
     _flush_finish()
-
-
-def take_pending(n: int):
-    """Remove and return up to ``n`` deferred reductions, for a launch that runs
-    them beside its own work (``mrec_emb_bwd_apply_ex``)."""
-    global _PENDING
-    jobs, _PENDING = _PENDING[:n], _PENDING[n:]
-    return jobs
-
-
-def co_reduce_args():
-    """Up to CO_REDUCE_MAX deferred reductions as the ``n_reduce, reduce`` arguments of a
-    launch that runs them beside its own work -> (n, GemmCall array or None, keep-alive).
-    The array points into the keep-alive: hold it until ``_mrec.call`` has returned."""
-    jobs = take_pending(CO_REDUCE_MAX)
-    arr = (_mrec.GemmCall * len(jobs))(*[j.struct() for j in jobs]) if jobs else None
-    return len(jobs), arr, jobs
 
 
 def _defer(call: "_Call"):
@@ -412,6 +400,98 @@ def dp_grads(*params):
     return out
 
 
+# A parameter's gradient goes to exactly one of three places:
+#   "sgd": plain SGD fused into the kernel that finishes the gradient (``sgd_lr``):
+#          the parameter is updated in place, the bf16 images it was handed are
+#          rewritten (``images_updated``) and autograd gets None;
+#   "dp":  the parameter's view of the data-parallel flat buffer (``dp_grads``), which
+#          IModel all-reduces once and applies with one mrec_sgd_multi; autograd
+#          gets None;
+#   "ret": a fresh fp32 tensor returned to autograd.
+# The parameters decided together share one destination: SGD when all of them have
+# one common lr, else DP when all of them have a view, else returned.
+_IMG_KIND = {"rowtr": _mrec.IMG_ROW_TR, "tower": _mrec.IMG_TOWER}
+
+
+def _decide(params, dp: bool = True):
+    """(lr, views) of ``params`` decided together: at most one is not None."""
+    lr = sgd_lr(*params)
+    return lr, (dp_grads(*params) if dp and lr is None else None)
+
+
+class _GradDest(NamedTuple):
+    """The destination of one (W, b) pair's gradients (see above): ``kw`` are the
+    destination's keyword arguments of the dW = dY^T [X | 1] GEMM (``_Call`` or
+    ``gemm``), ``dW`` / ``db`` what the backward returns to autograd."""
+    where: str
+    kw: dict
+    dW: Optional[torch.Tensor]
+    db: Optional[torch.Tensor]
+
+
+def _grad_dest(W, b, imgs, kind: str, decided=None) -> _GradDest:
+    """Where the gradients of W [N, K] and b [N] (or None) go.  ``imgs``: W's cached
+    ``kind`` images, which a fused update rewrites; ``decided``: (lr, (W's view, b's
+    view) or None) when the pair was decided with others, else ``_decide((W, b))``.
+    Call it when the GEMM is built: a fused update is announced here."""
+    lr, views = _decide((W, b)) if decided is None else decided
+    if lr is not None:
+        images_updated(W, kind)
+        kw = dict(out=W.detach(), ones_out=None if b is None else b.detach(),
+                  out_dtype=torch.float32, sgd_lr=lr, img_row=imgs[0], img_tr=imgs[1],
+                  img_kind=_IMG_KIND[kind])
+        return _GradDest("sgd", kw, None, None)
+    if views is not None:
+        kw = dict(out=views[0], ones_out=views[1], out_dtype=torch.float32)
+        return _GradDest("dp", kw, None, None)
+    dW = torch.empty(W.shape[0], W.shape[1], dtype=torch.float32, device=W.device)
+    db = None if b is None else torch.empty(W.shape[0], dtype=torch.float32, device=W.device)
+    return _GradDest("ret", dict(out=dW, ones_out=db, out_dtype=torch.float32), dW, db)
+
+
+_NO_GRAD = _GradDest("ret", {}, None, None)  # no weight gradient is wanted
+
+
+def _dx_dw(dy, x, wt, N: int, K: int, dest: _GradDest, want_dx: bool = True, **dx_epi):
+    """One layer's backward GEMMs over the M rows of dY [M, N] and x [M, K (+ pad)]:
+    dx = epi(dY W), shaped like x (B = the W^T image ``wt``; ``dx_epi``: its mask or
+    addend), when wanted, and dW, db = dY^T [x | 1] into ``dest``.  -> dx or None.
+
+      dx[m, k] = sum_n dY[m, n] W[n, k]: B(k'=n, col=k) = W^T[k*ld + n] -> ROW
+      dW[n, k] = sum_m dY[m, n] x[m, k]: A(i=n, red=m) = dY[m*ld + n] -> COL,
+      B(red=m, col=k) = x[m*ld + k] -> COL; ones column -> db
+
+    Returned gradients: plain mrec_gemm calls.  Else one mrec_gemm_multi launch that
+    also takes the pending reductions along: with split-K the dW GEMM leaves partial
+    slabs there and its reduction (with the update) is deferred to a later launch;
+    without it the whole dW GEMM runs beside the dx GEMM -- unless it updates in
+    place (fused SGD): its epilogue rewrites ``wt``, which the dx GEMM reads, so it
+    gets a launch of its own after it."""
+    M, K_x = x.shape
+    if dest.where == "ret":
+        dx = None
+        if want_dx:
+            flush_pending()
+            dx = gemm(dy, _mrec.LAYOUT_ROW, wt, _mrec.LAYOUT_ROW, M, K_x, N, b_cols=K, **dx_epi)
+        if dest is not _NO_GRAD:
+            gemm(dy, _mrec.LAYOUT_COL, x, _mrec.LAYOUT_COL, N, K, M, **dest.kw)
+        return dx
+    cdx = [_Call(dy, _mrec.LAYOUT_ROW, wt, _mrec.LAYOUT_ROW, M, K_x, N, _mrec.GEMM_FULL, b_cols=K,
+                 **dx_epi)] if want_dx else []
+    sk = _split_beside(N, K + 1, M)
+    cdw = _Call(dy, _mrec.LAYOUT_COL, x, _mrec.LAYOUT_COL, N, K, M,
+                _mrec.GEMM_PARTIAL if sk > 1 else _mrec.GEMM_FULL, split_k=sk, **dest.kw)
+    if sk > 1:
+        launch_multi(cdx + [cdw])
+        _defer(cdw)
+    elif dest.where == "dp":
+        launch_multi(cdx + [cdw])
+    else:
+        launch_multi(cdx)
+        launch_multi([cdw])
+    return cdx[0].out if cdx else None
+
+
 def _bf16_rows(t: torch.Tensor) -> torch.Tensor:
     """bf16 [M, N] with 16-byte aligned rows (what mrec_gemm requires); copies into
     an r8-padded buffer only when the input is not already laid out that way."""
@@ -427,6 +507,10 @@ def _bf16_rows(t: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _f32c(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    return None if t is None else t.detach().float().contiguous()
+
+
 def _weight_f32(w: torch.Tensor) -> torch.Tensor:
     w = w.detach()
     if w.dtype != torch.float32:
@@ -437,8 +521,7 @@ def _weight_f32(w: torch.Tensor) -> torch.Tensor:
 class _LinearFn(torch.autograd.Function):
     """y = act(x[:, :K] W^T + b) with W [N, K] fp32 (nn.Linear layout).
     x_relu: x is a ReLU output, so dx is masked by x in the dx GEMM's epilogue.
-    With fused SGD (sgd_lr) the weight-gradient GEMM applies W -= lr dW, b -= lr db
-    and rewrites the bf16 images; no gradient is returned."""
+    dW and db go where ``_grad_dest`` says."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, relu: bool, out_dtype, x_relu: bool):
@@ -447,11 +530,10 @@ class _LinearFn(torch.autograd.Function):
         N, K = weight.shape
         flush_pending()
         wr, wt = weight_images(weight)
-        b = bias.detach().float().contiguous() if bias is not None else None
-        y = gemm(x, _mrec.LAYOUT_ROW, wr[:, :K], _mrec.LAYOUT_ROW, M, N, K, bias=b,
+        y = gemm(x, _mrec.LAYOUT_ROW, wr[:, :K], _mrec.LAYOUT_ROW, M, N, K, bias=_f32c(bias),
                  act=_mrec.ACT_RELU if relu else _mrec.ACT_NONE, out_dtype=out_dtype)
         ctx.save_for_backward(x, y if relu else None)
-        ctx.relu, ctx.has_bias, ctx.NK, ctx.x_relu = relu, bias is not None, (N, K), x_relu
+        ctx.relu, ctx.NK, ctx.x_relu = relu, (N, K), x_relu
         ctx.y_ptr = y.data_ptr()
         ctx.weight, ctx.bias, ctx.wr, ctx.wt = weight, bias, wr, wt
         return y
@@ -459,63 +541,17 @@ class _LinearFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, y = ctx.saved_tensors
-        M, K_x = x.shape
         N, K = ctx.NK
         if ctx.relu and not _premasked(dy, ctx.y_ptr):
             dy = torch.where(y > 0, dy.to(y.dtype), torch.zeros((), dtype=y.dtype, device=y.device))
         dy = _bf16_rows(dy)
-        dx = dW = db = None
         need_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        lr = sgd_lr(ctx.weight, ctx.bias) if need_w else None
-        dpg = dp_grads(ctx.weight, ctx.bias) if need_w and lr is None else None
-        if lr is not None or dpg is not None:
-            # one launch: dx GEMM + dW partial slabs (+ earlier layers' deferred dW
-            # reductions); this layer's reduction + SGD runs in the next launch.
-            # Data-parallel: the reduction writes dW / db into the flat gradient
-            # buffer that IModel all-reduces (then one mrec_sgd_multi updates)
-            calls = []
-            if ctx.needs_input_grad[0]:
-                cdx = _Call(dy, _mrec.LAYOUT_ROW, ctx.wt, _mrec.LAYOUT_ROW, M, K_x, N,
-                            _mrec.GEMM_FULL, b_cols=K, mask=x if ctx.x_relu else None)
-                calls.append(cdx)
-                dx = cdx.out
-            sk = _split_beside(N, K + 1, M)
-            if dpg is not None:
-                cdw = _Call(dy, _mrec.LAYOUT_COL, x, _mrec.LAYOUT_COL, N, K, M,
-                            _mrec.GEMM_PARTIAL if sk > 1 else _mrec.GEMM_FULL,
-                            ones_out=dpg[1], out=dpg[0], out_dtype=torch.float32, split_k=sk)
-            else:
-                cdw = _Call(dy, _mrec.LAYOUT_COL, x, _mrec.LAYOUT_COL, N, K, M,
-                            _mrec.GEMM_PARTIAL if sk > 1 else _mrec.GEMM_FULL,
-                            ones_out=ctx.bias.detach() if ctx.has_bias else None,
-                            out=ctx.weight.detach(), out_dtype=torch.float32, split_k=sk,
-                            sgd_lr=lr, img_row=ctx.wr, img_tr=ctx.wt)
-                images_updated(ctx.weight, "rowtr")
-            if sk > 1:
-                launch_multi(calls + [cdw])
-                _defer(cdw)
-            elif dpg is not None:  # plain dW output: independent of the dx GEMM
-                launch_multi(calls + [cdw])
-            else:  # the dW epilogue rewrites wt, which the dx GEMM reads: two launches
-                launch_multi(calls)
-                launch_multi([cdw])
-            if ctx.x_relu and dx is not None:
-                _stamp(dx, x)
-            return dx, None, None, None, None, None
-        if ctx.needs_input_grad[0]:
-            # dx[m, k] = sum_n dZ[m, n] W[n, k]; B(k'=n, col=k) = W^T[k*ld + n] -> ROW
-            flush_pending()
-            dx = gemm(dy, _mrec.LAYOUT_ROW, ctx.wt, _mrec.LAYOUT_ROW, M, K_x, N, b_cols=K,
-                      mask=x if ctx.x_relu else None, out_dtype=_BF16)
-            if ctx.x_relu:
-                _stamp(dx, x)
-        if need_w:
-            # dW[n, k] = sum_m dZ[m, n] x[m, k]: A(i=n, red=m) = dy[m*ld + n] -> COL,
-            # B(red=m, col=k) = x[m*ld + k] -> COL; ones column -> db
-            dW = torch.empty(N, K, dtype=torch.float32, device=dy.device)
-            db = torch.empty(N, dtype=torch.float32, device=dy.device) if ctx.has_bias else None
-            gemm(dy, _mrec.LAYOUT_COL, x, _mrec.LAYOUT_COL, N, K, M, ones_out=db, out=dW)
-        return dx, dW, db, None, None, None
+        dest = _grad_dest(ctx.weight, ctx.bias, (ctx.wr, ctx.wt), "rowtr") if need_w else _NO_GRAD
+        dx = _dx_dw(dy, x, ctx.wt, N, K, dest, ctx.needs_input_grad[0],
+                    mask=x if ctx.x_relu else None)
+        if ctx.x_relu and dx is not None:
+            _stamp(dx, x)
+        return dx, dest.dW, dest.db, None, None, None
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
@@ -534,6 +570,17 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
     return y
 
 
+def _cross_fwd(x0, xl, W, b):
+    """x0 * (x_l W^T + b) + x_l as one GEMM -> (it, z = x_l W^T + b, W's row and
+    transposed images)."""
+    M, d = xl.shape[0], W.shape[0]
+    wr, wt = weight_images(W)
+    z = _alloc(M, d, _BF16, xl.device)
+    out = gemm(xl, _mrec.LAYOUT_ROW, wr[:, :d], _mrec.LAYOUT_ROW, M, d, d, bias=_f32c(b), mul=x0,
+               add=xl, aux=z)
+    return out, z, wr, wt
+
+
 class _CrossFn(torch.autograd.Function):
     """DCN-v2 layer x_{l+1} = x0 * (x_l W^T + b) + x_l (one GEMM, epilogue fused;
     z = x_l W^T + b kept for the backward)."""
@@ -541,15 +588,8 @@ class _CrossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, xl, weight, bias):
         x0, xl = _bf16_rows(x0), _bf16_rows(xl)
-        M = xl.shape[0]
-        d = weight.shape[0]
-        wr, wt = weight_images(weight)
-        b = bias.detach().float().contiguous() if bias is not None else None
-        z = _alloc(M, d, _BF16, xl.device)
-        out = gemm(xl, _mrec.LAYOUT_ROW, wr[:, :d], _mrec.LAYOUT_ROW, M, d, d, bias=b, mul=x0,
-                   add=xl, aux=z)
+        out, z, wr, wt = _cross_fwd(x0, xl, weight, bias)
         ctx.save_for_backward(x0, xl, z)
-        ctx.has_bias = bias is not None
         ctx.weight, ctx.bias, ctx.wr, ctx.wt = weight, bias, wr, wt
         return out
 
@@ -567,21 +607,14 @@ class _CrossFn(torch.autograd.Function):
             dz.as_strided((M, dz.stride(0) - d), (dz.stride(0), 1), d).zero_()
         dxl = gemm(dz, _mrec.LAYOUT_ROW, wt, _mrec.LAYOUT_ROW, M, xl.shape[1], d, b_cols=d,
                    add=_pad_cols(g, xl.shape[1]))
-        dW = db = None
-        lr = sgd_lr(ctx.weight, ctx.bias)
-        if lr is not None:
-            gemm(dz, _mrec.LAYOUT_COL, xl, _mrec.LAYOUT_COL, d, d, M,
-                 ones_out=ctx.bias.detach() if ctx.has_bias else None, out=ctx.weight.detach(),
-                 out_dtype=torch.float32, sgd_lr=lr, img_row=ctx.wr, img_tr=ctx.wt)
-            images_updated(ctx.weight, "rowtr")
-        else:
-            dW = torch.empty(d, d, dtype=torch.float32, device=g.device)
-            db = torch.empty(d, dtype=torch.float32, device=g.device) if ctx.has_bias else None
-            gemm(dz, _mrec.LAYOUT_COL, xl, _mrec.LAYOUT_COL, d, d, M, ones_out=db, out=dW)
+        # fused SGD or returned: this single-layer op has no data-parallel destination
+        dest = _grad_dest(ctx.weight, ctx.bias, (ctx.wr, wt), "rowtr",
+                          _decide((ctx.weight, ctx.bias), dp=False))
+        gemm(dz, _mrec.LAYOUT_COL, xl, _mrec.LAYOUT_COL, d, d, M, **dest.kw)
         dx0 = (g.float() * z.float()).to(_BF16)
         if x0.shape[1] > d:
             dx0 = F.pad(dx0, (0, x0.shape[1] - d))
-        return dx0, dxl, dW, db
+        return dx0, dxl, dest.dW, dest.db
 
 
 class _CrossNetFn(torch.autograd.Function):
@@ -589,8 +622,8 @@ class _CrossNetFn(torch.autograd.Function):
     l = 0..L-1, as one autograd node: forward = one fused GEMM per layer; backward
     per layer = ONE elementwise kernel (mrec_dcn_cross_bwd_prep: dz = g*x0 and the
     fp32 sum over layers of g*z, i.e. x0's multiplier gradient) + the dx_l GEMM
-    (layer 0 adds that sum, so its output is dx0) + the dW GEMM (fused SGD when
-    compiled with plain SGD, data-parallel gradient views, else returned)."""
+    (layer 0 adds that sum, so its output is dx0) + the dW GEMM (``_grad_dest`` per
+    layer)."""
 
     @staticmethod
     def forward(ctx, x0, n, *params):
@@ -599,13 +632,7 @@ class _CrossNetFn(torch.autograd.Function):
         xl = x0
         saved = []
         for W, b in zip(weights, biases):
-            M = xl.shape[0]
-            d = W.shape[0]
-            wr, wt = weight_images(W)
-            bb = b.detach().float().contiguous() if b is not None else None
-            z = _alloc(M, d, _BF16, xl.device)
-            out = gemm(xl, _mrec.LAYOUT_ROW, wr[:, :d], _mrec.LAYOUT_ROW, M, d, d, bias=bb,
-                       mul=x0, add=xl, aux=z)
+            out, z, wr, wt = _cross_fwd(x0, xl, W, b)
             saved.append((xl, z, wr, wt))
             xl = out
         ctx.x0, ctx.saved, ctx.weights, ctx.biases = x0, saved, weights, biases
@@ -632,41 +659,9 @@ class _CrossNetFn(torch.autograd.Function):
                        _mrec.stream_handle())
             # dx_l = dz W (+ g: x_l feeds the residual; layer 0: + sum_l g_l*z_l too)
             add = addend if l == 0 else _pad_cols(g, xl.shape[1])
-            lr = sgd_lr(W, b)
-            dpg = dp_grads(W, b) if lr is None else None
-            if lr is not None or dpg is not None:
-                # one launch: dx GEMM + dW split-K slabs (+ the previous layer's deferred
-                # dW reduction); this layer's reduction rides in the next launch
-                cdx = _Call(dz, _mrec.LAYOUT_ROW, wt, _mrec.LAYOUT_ROW, M, xl.shape[1], d,
-                            _mrec.GEMM_FULL, b_cols=d, add=add)
-                sk = _split_beside(d, d + 1, M)
-                ph = _mrec.GEMM_PARTIAL if sk > 1 else _mrec.GEMM_FULL
-                if dpg is not None:
-                    cdw = _Call(dz, _mrec.LAYOUT_COL, xl, _mrec.LAYOUT_COL, d, d, M, ph,
-                                ones_out=dpg[1], out=dpg[0], out_dtype=torch.float32, split_k=sk)
-                else:
-                    cdw = _Call(dz, _mrec.LAYOUT_COL, xl, _mrec.LAYOUT_COL, d, d, M, ph,
-                                ones_out=b.detach() if b is not None else None, out=W.detach(),
-                                out_dtype=torch.float32, split_k=sk, sgd_lr=lr, img_row=wr,
-                                img_tr=wt)
-                    images_updated(W, "rowtr")
-                if sk > 1:
-                    launch_multi([cdx, cdw])
-                    _defer(cdw)
-                elif dpg is not None:
-                    launch_multi([cdx, cdw])
-                else:  # the dW epilogue rewrites wt, which the dx GEMM reads
-                    launch_multi([cdx])
-                    launch_multi([cdw])
-                g = cdx.out
-                continue
-            flush_pending()
-            gx = gemm(dz, _mrec.LAYOUT_ROW, wt, _mrec.LAYOUT_ROW, M, xl.shape[1], d, b_cols=d,
-                      add=add)
-            dWs[l] = torch.empty(d, d, dtype=torch.float32, device=g.device)
-            dbs[l] = torch.empty(d, dtype=torch.float32, device=g.device) if b is not None else None
-            gemm(dz, _mrec.LAYOUT_COL, xl, _mrec.LAYOUT_COL, d, d, M, ones_out=dbs[l], out=dWs[l])
-            g = gx
+            dest = _grad_dest(W, b, (wr, wt), "rowtr")
+            dWs[l], dbs[l] = dest.dW, dest.db
+            g = _dx_dw(dz, xl, wt, d, d, dest, add=add)
         ctx.saved = None
         return (g, None, *dWs, *dbs)
 
@@ -1057,12 +1052,38 @@ def grad_one(dev) -> torch.Tensor:
     return t
 
 
+def _head_param_grads(part, B: int, H: int, ns: int, g, one: bool, head):
+    """The gradients of a CTR head's (w, b, ws, b2) from the partials ``part`` of the
+    kernel that ran its forward (fixed-order sums), scaled by the loss gradient ``g``
+    (``one``: g is ``grad_one``, no scaling) -> (dW, db, dws, db2) for autograd.
+    Fused SGD and the data-parallel flat buffer defer the finish: it is independent
+    of the backward GEMMs and rides along the next launch (all None is returned);
+    returned gradients are finished now."""
+    w, b, ws, b2 = head
+    lr, views = _decide(head)
+    gs = None if one else g
+    if lr is not None and w.is_contiguous():
+        defer_head_finish(_HeadFinish(part, B, H, ns, gs, lr=lr, params=[
+            None if t is None else t.detach() for t in head]))
+        return None, None, None, None
+    if views is not None:
+        defer_head_finish(_HeadFinish(part, B, H, ns, gs, grads=views))
+        return None, None, None, None
+    f32 = dict(dtype=torch.float32, device=part.device)
+    dW = torch.empty(1, H, **f32)
+    db = torch.empty(1, **f32) if b is not None else None
+    dws = torch.empty(ns, **f32) if ws is not None else None
+    db2 = torch.empty(1, **f32) if b2 is not None else None
+    _HeadFinish(part, B, H, ns, g, grads=[dW, db, dws, db2]).run()
+    return dW, db, dws, db2
+
+
 class _CTRHeadBCEFn(torch.autograd.Function):
     """loss = BCEWithLogits(base + h W^T + b [+ xs ws + b2], y) (mean) for a
     Linear(H, 1) head (+ an optional side linear term: DeepFM's dense first-order
     weight and global bias).  The forward kernel also produces dh, dz and the
-    parameter-gradient partials; the backward only reduces the partials (fused SGD
-    of W, b, ws, b2 when compiled with plain SGD)."""
+    parameter-gradient partials; the backward only reduces the partials
+    (``_head_param_grads``)."""
 
     @staticmethod
     def forward(ctx, h, weight, bias, base, ws, b2, y, xs, h_relu: bool):
@@ -1110,27 +1131,8 @@ class _CTRHeadBCEFn(torch.autograd.Function):
         dev = part.device
         g = gloss.detach().float().reshape(1).contiguous()
         one = g.data_ptr() == grad_one(dev).data_ptr()
-        lr = sgd_lr(ctx.weight, ctx.bias, ctx.ws, ctx.b2)
-        dW = db = dws = db2 = None
-        det = (lambda t: None if t is None else t.detach())
-        dpg = dp_grads(ctx.weight, ctx.bias, ctx.ws, ctx.b2) if lr is None else None
-        if lr is not None and ctx.weight.is_contiguous():
-            # independent of the backward GEMMs: rides along the next one
-            defer_head_finish(_HeadFinish(part, ctx.B, ctx.H, ctx.ns, None if one else g, lr,
-                                          ctx.weight.detach(), det(ctx.bias), det(ctx.ws),
-                                          det(ctx.b2)))
-        elif dpg is not None:
-            defer_head_finish(_HeadFinish(part, ctx.B, ctx.H, ctx.ns, None if one else g, None,
-                                          None, None, None, None, grads=dpg))
-        else:
-            f32 = dict(dtype=torch.float32, device=dev)
-            dW = torch.empty(1, ctx.H, **f32)
-            db = torch.empty(1, **f32) if ctx.bias is not None else None
-            dws = torch.empty(ctx.ns, **f32) if ctx.ws is not None else None
-            db2 = torch.empty(1, **f32) if ctx.b2 is not None else None
-            _mrec.call("mrec_ctr_head_finish", part.data_ptr(), part.stride(0), ctx.B, ctx.H,
-                       ctx.ns, g.data_ptr(), 0, 0.0, None, None, None, None, dW.data_ptr(),
-                       _mrec.ptr(db), _mrec.ptr(dws), _mrec.ptr(db2), _mrec.stream_handle())
+        dW, db, dws, db2 = _head_param_grads(part, ctx.B, ctx.H, ctx.ns, g, one,
+                                             (ctx.weight, ctx.bias, ctx.ws, ctx.b2))
         if not one:
             dh = (dh.float() * g).to(_BF16)
             dz = dz * g
@@ -1174,26 +1176,24 @@ def tower_supported(x0: torch.Tensor, mlp, head: torch.nn.Linear, xs=None, cross
     Dense.py:4-24) with dropout 0 (or eval) + Linear(N_L, 1) + BCE on the GPU, and
     up to 3 DCN-v2 cross layers (``nn.Linear(d, d)``, d = the MLP's input width)
     ahead of it when the batch takes mrec_tower_dw."""
+    dense_layers = list(mlp.mlp) if hasattr(mlp, "mlp") else []
+    lins = [d.linear for d in dense_layers]
+    widths = [lins[0].in_features] + [l.out_features for l in lins] if lins else []
     if cross:
-        lins = _mlp_linears(mlp) if (hasattr(mlp, "mlp") and mlp.mlp) else None
         if not lins or len(cross) > TOWER_MAXC:
             return False
-        d = lins[0].in_features
+        d = widths[0]
         if any(c.in_features != d or c.out_features != d or c.weight.dtype != torch.float32
                or not c.weight.is_contiguous() for c in cross):
             return False
-        widths = [d] * len(cross) + [d] + [l.out_features for l in lins]
-        if not _tdw_splits(x0.shape[0], widths):
+        if not _tdw_splits(x0.shape[0], [d] * len(cross) + widths):
             return False
     if not (TOWER and x0.is_cuda and torch.is_grad_enabled() and x0.dtype == _BF16):
         return False
-    dense_layers = list(mlp.mlp) if hasattr(mlp, "mlp") else None
     if not dense_layers or len(dense_layers) > TOWER_MAXL:
         return False
     if any(d.dropout.p > 0 and d.training for d in dense_layers):
         return False
-    lins = [d.linear for d in dense_layers]
-    widths = [lins[0].in_features] + [l.out_features for l in lins]
     if any(w > TOWER_MAXW for w in widths) or head.out_features != 1:
         return False
     if any(l.weight.dtype != torch.float32 or not l.weight.is_contiguous() for l in lins):
@@ -1239,20 +1239,81 @@ def _split_tower(widths, K: int) -> int:
     """K slices of the tower's weight-gradient GEMMs (generic mrec_gemm_multi path,
     dW_l [N_l, K_l + 1] over the batch), which share one launch: about two residency
     waves of 256-thread workgroups (3 per CU), slices of >= 256 rows."""
-    tiles = sum(((widths[l + 1] + 63) // 64) * ((widths[l] + 1 + 63) // 64)
-                for l in range(len(widths) - 1))
+    tiles = _tdw_tiles(widths)
     s = 1
     while tiles * (s + 1) <= 640 and K // (s + 1) >= 256 and s < 64:
         s += 1
     return s
 
 
+class _TowerBufs(NamedTuple):
+    """What a tower launch with a backward half writes: the activations h_l (all but
+    the last), the pre-activation gradients dh_l, the cross layers' x_c / dz_c and
+    x0's image (k-fragment images only), and dx0 (None when not needed)."""
+    hs: list
+    dhs: list
+    x0_img: Optional[torch.Tensor]
+    cx_imgs: list
+    cdz_imgs: list
+    dx0: Optional[torch.Tensor]
+
+
+def _tower_buffers(x0, widths, tdw: int, need_dx0: bool, C: int = 0) -> _TowerBufs:
+    """The weight gradients' operands are k-fragment images for mrec_tower_dw
+    (``tdw``: the tower writes them, x0's and the C cross layers' too), else
+    row-major ``_alloc`` rows for the generic GEMM."""
+    B, dev = x0.shape[0], x0.device
+    L = len(widths) - 1
+    if tdw:
+        def buf(n):
+            return torch.empty(int(_mrec.lib().mrec_kfrag_elems(B, n)), dtype=_BF16, device=dev)
+    else:
+        def buf(n):
+            return _alloc(B, n, _BF16, dev)
+    hs = [buf(widths[l + 1]) for l in range(L - 1)]
+    dhs = [buf(widths[l + 1]) for l in range(L)]
+    x0_img = buf(widths[0]) if tdw else None
+    cx_imgs = [buf(widths[0]) for _ in range(C if tdw else 0)]
+    cdz_imgs = [buf(widths[0]) for _ in range(C if tdw else 0)]
+    dx0 = None
+    if need_dx0:  # x0's shape: it may carry pad columns past K0, which get a zero gradient
+        Kx = x0.shape[1]
+        dx0 = (_alloc(B, Kx, _BF16, dev) if _r8(Kx) == _r8(widths[0]) else
+               torch.zeros(B, _r8(Kx), dtype=_BF16, device=dev)[:, :Kx])
+    return _TowerBufs(hs, dhs, x0_img, cx_imgs, cdz_imgs, dx0)
+
+
+def _tower_args(x0, widths, imgs, bsd, hw, hb, bufs: Optional[_TowerBufs] = None, part=None):
+    """mrec_tower_args: the MLP and its head, plus (``bufs``, ``part``) the outputs of a
+    launch with a backward half.  The mode and what only one mode takes (labels,
+    side term, loss, cross layers; scores; dz_in) are the caller's to fill."""
+    a = _mrec.TowerArgs()
+    L = len(widths) - 1
+    a.batch, a.n_layers = x0.shape[0], L
+    for l in range(L + 1):
+        a.width[l] = widths[l]
+    a.x0, a.ld_x0 = x0.data_ptr(), x0.stride(0)
+    for l in range(L):
+        a.w_fwd[l], a.w_bwd[l] = imgs[l][0].data_ptr(), imgs[l][1].data_ptr()
+        a.bias[l] = _mrec.ptr(bsd[l])
+    a.head_w, a.head_b = hw.data_ptr(), _mrec.ptr(hb)
+    if bufs is not None:
+        for l in range(L):
+            a.dh_out[l], a.ld_dh[l] = bufs.dhs[l].data_ptr(), bufs.dhs[l].stride(0)
+            if l < L - 1:
+                a.h_out[l], a.ld_h[l] = bufs.hs[l].data_ptr(), bufs.hs[l].stride(0)
+        a.kfrag, a.x0_img = int(bufs.x0_img is not None), _mrec.ptr(bufs.x0_img)
+        a.dx0 = _mrec.ptr(bufs.dx0)
+        a.ld_dx0 = bufs.dx0.stride(0) if bufs.dx0 is not None else 0
+        a.part, a.ldp = part.data_ptr(), part.stride(0)
+    return a
+
+
 class _TowerBCEFn(torch.autograd.Function):
     """loss = BCEWithLogits(MLP(x0) . w + b + base [+ xs . ws + b2], y) (mean).
     Forward = ONE mrec_tower_fwd_bwd launch, which also produces every input /
     pre-activation gradient (dx0, dz, dh_l); backward = the weight-gradient GEMMs
-    (one mrec_gemm_multi launch with the head finish; fused SGD when compiled with
-    plain SGD, the split-K reductions ride in the next launch)."""
+    (``_tower_param_grads``: one launch with the head finish)."""
 
     @staticmethod
     def forward(ctx, x0, base, xs, y, n_layers, n_cross, *params):
@@ -1265,31 +1326,12 @@ class _TowerBCEFn(torch.autograd.Function):
         widths = [Ws[0].shape[1]] + [W.shape[0] for W in Ws]
         imgs = [tower_images(W) for W in Ws]
         cimgs = [tower_images(W) for W in cWs]
-        # the weight gradients' operands: k-fragment images for mrec_tower_dw (the
-        # tower writes them, x0's too), else row-major for the generic GEMM
         need_w = any(ctx.needs_input_grad[6:6 + 2 * L]) or any(
             ctx.needs_input_grad[6 + 2 * L + 4:6 + 2 * L + 4 + 2 * C])
         tdw = _tdw_splits(B, [widths[0]] * C + widths) if need_w else 0
         if C and need_w and not tdw:
             raise ValueError("cross layers in the tower need mrec_tower_dw (tower_supported)")
-        cx_imgs, cdz_imgs = [], []
-        if tdw:
-            kf = lambda n: torch.empty(int(_mrec.lib().mrec_kfrag_elems(B, n)), dtype=_BF16,  # noqa: E731
-                                       device=dev)
-            hs = [kf(widths[l + 1]) for l in range(L - 1)]
-            dhs = [kf(widths[l + 1]) for l in range(L)]
-            x0_img = kf(widths[0])
-            cx_imgs = [kf(widths[0]) for _ in range(C)]
-            cdz_imgs = [kf(widths[0]) for _ in range(C)]
-        else:
-            hs = [_alloc(B, widths[l + 1], _BF16, dev) for l in range(L - 1)]
-            dhs = [_alloc(B, widths[l + 1], _BF16, dev) for l in range(L)]
-            x0_img = None
-        dx0 = None
-        if ctx.needs_input_grad[0]:  # x0's shape (it may carry zero pad columns past K0)
-            Kx = x0.shape[1]
-            dx0 = (_alloc(B, Kx, _BF16, dev) if _r8(Kx) == _r8(widths[0]) else
-                   torch.zeros(B, _r8(Kx), dtype=_BF16, device=dev)[:, :Kx])
+        bufs = _tower_buffers(x0, widths, tdw, ctx.needs_input_grad[0], C)
         dz = torch.empty(B, dtype=torch.float32, device=dev)
         ns = 0 if xs is None else xs.shape[1]
         if xs is not None:
@@ -1302,43 +1344,27 @@ class _TowerBCEFn(torch.autograd.Function):
         part = torch.empty(nparts, ldp, dtype=torch.float32, device=dev)
         loss_part = torch.empty(nparts, dtype=torch.float32, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        f32 = lambda t: None if t is None else t.detach().float().contiguous()  # noqa: E731
-        hw, hb, wsd, b2d = f32(head_w).reshape(-1), f32(head_b), f32(ws), f32(b2)
-        bsd = [f32(b) for b in bs]
-        base_c = f32(base)
-        yc = y.detach().float().contiguous()
-        a = _mrec.TowerArgs()
-        a.batch, a.n_layers = B, L
-        for l in range(L + 1):
-            a.width[l] = widths[l]
-        a.x0, a.ld_x0 = x0.data_ptr(), x0.stride(0)
-        for l in range(L):
-            a.w_fwd[l], a.w_bwd[l] = imgs[l][0].data_ptr(), imgs[l][1].data_ptr()
-            a.bias[l] = _mrec.ptr(bsd[l])
-            a.dh_out[l], a.ld_dh[l] = dhs[l].data_ptr(), dhs[l].stride(0)
-            if l < L - 1:
-                a.h_out[l], a.ld_h[l] = hs[l].data_ptr(), hs[l].stride(0)
-        a.kfrag, a.x0_img = int(bool(tdw)), _mrec.ptr(x0_img)
-        cbsd = [f32(b) for b in cbs]
+        hw, hb, wsd, b2d = _f32c(head_w).reshape(-1), _f32c(head_b), _f32c(ws), _f32c(b2)
+        bsd, cbsd = [_f32c(b) for b in bs], [_f32c(b) for b in cbs]
+        base_c, yc = _f32c(base), _f32c(y)
+        a = _tower_args(x0, widths, imgs, bsd, hw, hb, bufs, part)
         a.n_cross = C
         for c in range(C):
             a.cross_w_fwd[c], a.cross_w_bwd[c] = cimgs[c][0].data_ptr(), cimgs[c][1].data_ptr()
             a.cross_bias[c] = _mrec.ptr(cbsd[c])
             if tdw:
-                a.cross_x_img[c], a.cross_dz_img[c] = cx_imgs[c].data_ptr(), cdz_imgs[c].data_ptr()
-        a.head_w, a.head_b, a.base = hw.data_ptr(), _mrec.ptr(hb), _mrec.ptr(base_c)
+                a.cross_x_img[c] = bufs.cx_imgs[c].data_ptr()
+                a.cross_dz_img[c] = bufs.cdz_imgs[c].data_ptr()
+        a.base = _mrec.ptr(base_c)
         a.xs, a.ld_xs, a.ns = _mrec.ptr(xs), xs.stride(0) if xs is not None else 0, ns
         a.ws, a.b2, a.y = _mrec.ptr(wsd), _mrec.ptr(b2d), yc.data_ptr()
-        a.dx0, a.ld_dx0 = _mrec.ptr(dx0), dx0.stride(0) if dx0 is not None else 0
         a.z, a.dz = None, dz.data_ptr()
-        a.part, a.ldp = part.data_ptr(), ldp
         a.loss_part, a.ticket, a.loss = loss_part.data_ptr(), _ticket(dev).data_ptr(), loss.data_ptr()
-        with _timed("mrec_tower_fwd_bwd"):
-            _mrec.call("mrec_tower_fwd_bwd", ctypes.byref(a), _mrec.stream_handle())
-        ctx.save_for_backward(x0 if x0_img is None else x0_img, dz, part, dx0, *hs, *dhs, *cx_imgs,
-                              *cdz_imgs)
-        ctx.L, ctx.C, ctx.B, ctx.H, ctx.ns, ctx.widths = L, C, B, H, ns, widths
-        ctx.tdw = tdw
+        _mrec.call("mrec_tower_fwd_bwd", ctypes.byref(a), _mrec.stream_handle())
+        ctx.save_for_backward(x0 if bufs.x0_img is None else bufs.x0_img, dz, part, bufs.dx0,
+                              *bufs.hs, *bufs.dhs, *bufs.cx_imgs, *bufs.cdz_imgs)
+        ctx.L, ctx.C, ctx.B, ctx.ns, ctx.widths = L, C, B, ns, widths
+        ctx.tdw, ctx.need_w = tdw, need_w
         ctx.Ws, ctx.bs, ctx.imgs = Ws, bs, imgs
         ctx.cWs, ctx.cbs, ctx.cimgs = cWs, cbs, cimgs
         ctx.head = (head_w, head_b, ws, b2)
@@ -1364,145 +1390,84 @@ class _TowerBCEFn(torch.autograd.Function):
             dhs = [(d.float() * g).to(_BF16) if tdw else _bf16_rows((d.float() * g).to(_BF16))
                    for d in dhs]
             cdz_imgs = [(d.float() * g).to(_BF16) for d in cdz_imgs]
-        cross = None
-        if C:  # cross layer c: dW = dz_c^T [x_c | 1]; the MLP's first X is x_C
-            d = ctx.widths[0]
-            cross = (ctx.cWs, ctx.cbs, ctx.cimgs, [(d, d)] * C, cdz_imgs, [x0] + cx_imgs[:-1])
-            if tdw:
-                x0 = cx_imgs[-1]
-        need_w = any(ctx.needs_input_grad[6:6 + 2 * L]) or any(
-            ctx.needs_input_grad[6 + 2 * L + 4:6 + 2 * L + 4 + 2 * C])
-        grads = _tower_param_grads(ctx.widths, ctx.Ws, ctx.bs, ctx.imgs, ctx.head, B, ctx.H, ctx.ns,
-                                   x0, hs, dhs, part, g, one, tdw, need_w, cross=cross)
-        dWs, dbs, (dW_h, db_h, dws, db2), (cdWs, cdbs) = grads
-        return (dx0, dz if ctx.has_base else None, None, None, None, None, *dWs, *dbs,
-                dW_h, db_h, dws, db2, *cdWs, *cdbs)
+        # cross layer c: dW = dz_c^T [x_c | 1] from the images x_0 .. x_{C-1} (tdw only);
+        # the MLP's first X is x_C
+        xc = [x0] + cx_imgs
+        lay = [(ctx.cWs[c], ctx.cbs[c], ctx.cimgs[c], cdz_imgs[c] if tdw else None,
+                xc[c] if tdw else None) for c in range(C)]
+        xin = [xc[C] if tdw else x0[:, :ctx.widths[0]]] + hs
+        lay += list(zip(ctx.Ws, ctx.bs, ctx.imgs, dhs, xin))
+        dWs, dbs, head_grads = _tower_param_grads(lay, ctx.head, part, B, ctx.ns, g, one, tdw,
+                                                  ctx.need_w)
+        return (dx0, dz if ctx.has_base else None, None, None, None, None, *dWs[C:], *dbs[C:],
+                *head_grads, *dWs[:C], *dbs[:C])
 
 
-def _tower_param_grads(widths, Ws, bs, imgs, head, B: int, H: int, ns: int, x0, hs, dhs, part, g,
-                       one: bool, tdw: int, need_w: bool, cross=None):
-    """The weight-gradient tail of a fused tower (BCE and given-dz modes): the L
-    layers' dW = dh^T [h | 1] (mrec_tower_dw from the k-fragment images, else the
-    generic split-K GEMMs) + the head parameters from the tower's partials; fused
-    SGD / flat DP buffer / returned gradients as the parameters ask.  ``cross``
-    (Ws, bs, imgs, dims, dys, xs): the cross layers ahead of the MLP, their dW =
-    dz^T [x | 1] in the same mrec_tower_dw launch (tdw required).  ->
-    (dWs, dbs, (dW_h, db_h, dws, db2), (cross dWs, cross dbs)), None where not
-    returned."""
-    head_w, head_b, ws, b2 = head
-    L = len(Ws)
-    dev = part.device
-    xin = ([x0] if tdw else [x0[:, :widths[0]]]) + hs
-    # every layer of the launch: (W, b, images, N, K, dY, X); cross layers first
-    lay = []
-    if cross is not None:
-        cW, cb, cim, cdims, cdy, cx = cross
-        lay += [(cW[c], cb[c], cim[c], cdims[c][0], cdims[c][1], cdy[c] if tdw else None,
-                 cx[c] if tdw else None) for c in range(len(cW))]
-    C = len(lay)
-    lay += [(Ws[l], bs[l], imgs[l], widths[l + 1], widths[l], dhs[l], xin[l]) for l in range(L)]
-    # --- weight gradients of the layers: one launch ---
-    lr = sgd_lr(*[t[0] for t in lay], *[t[1] for t in lay])
-    dpg = dp_grads(*[t[0] for t in lay], *[t[1] for t in lay]) if lr is None else None
+def _tower_param_grads(lay, head, part, B: int, ns: int, g, one: bool, tdw: int, need_w: bool):
+    """The weight-gradient tail of a fused tower (BCE and given-dz modes).  ``lay``:
+    every layer of the launch as (W [N, K], b, tower images, dY, X), cross layers
+    ahead of the MLP's; their dW = dY^T [X | 1] by mrec_tower_dw from the k-fragment
+    images dY, X (``tdw`` slices), else by the generic split-K GEMMs from the rows
+    dY [B, N], X [B, K]; one destination for all of them (``_decide``).  Then the head
+    parameters from the tower's partials (``_head_param_grads``).  ->
+    (dWs, dbs, (dW_h, db_h, dws, db2)), None where not returned."""
+    # --- weight gradients of the layers: one launch, one destination for all ---
     n = len(lay)
+    lr, views = _decide([t[0] for t in lay] + [t[1] for t in lay])
+    returned = lr is None and views is None
     dWs, dbs = [None] * n, [None] * n
     calls = []
     if need_w:
-        sk = tdw or _split_tower(widths, B)
+        sk = tdw or _split_tower([lay[0][0].shape[1]] + [t[0].shape[0] for t in lay], B)
         ph = _mrec.GEMM_PARTIAL if sk > 1 else _mrec.GEMM_FULL
         # with mrec_tower_dw the calls below only carry the REDUCE phase's
         # arguments (its operands are never read: k-fragment images as stand-ins)
         opnd = (lambda t: t.view(-1, 8)) if tdw else (lambda t: t)  # noqa: E731
-        for i, (W, bias_l, img, N, K, dy, xx) in enumerate(lay):
-            if lr is not None:
-                c = _Call(opnd(dy), _mrec.LAYOUT_COL, opnd(xx), _mrec.LAYOUT_COL, N, K, B, ph,
-                          ones_out=bias_l.detach() if bias_l is not None else None,
-                          out=W.detach(), out_dtype=torch.float32, split_k=sk, sgd_lr=lr,
-                          img_row=img[0], img_tr=img[1], img_kind=_mrec.IMG_TOWER)
-                images_updated(W, "tower")
-            elif dpg is not None:
-                c = _Call(opnd(dy), _mrec.LAYOUT_COL, opnd(xx), _mrec.LAYOUT_COL, N, K, B, ph,
-                          ones_out=dpg[n + i], out=dpg[i], out_dtype=torch.float32,
-                          split_k=sk)
-            else:
-                dWs[i] = torch.empty(N, K, dtype=torch.float32, device=dev)
-                dbs[i] = (torch.empty(N, dtype=torch.float32, device=dev)
-                          if bias_l is not None else None)
-                c = _Call(opnd(dy), _mrec.LAYOUT_COL, opnd(xx), _mrec.LAYOUT_COL, N, K, B, ph,
-                          ones_out=dbs[i], out=dWs[i], out_dtype=torch.float32, split_k=sk)
-            calls.append(c)
-    # --- the head's parameters (w, b, ws, b2): fixed-order partial sums ---
-    hlr = sgd_lr(head_w, head_b, ws, b2)
-    det = (lambda t: None if t is None else t.detach())
-    hdp = dp_grads(head_w, head_b, ws, b2) if hlr is None else None
-    dW_h = db_h = dws = db2 = None
-    if hlr is not None and head_w.is_contiguous():
-        defer_head_finish(_HeadFinish(part, B, H, ns, None if one else g, hlr,
-                                      head_w.detach(), det(head_b), det(ws), det(b2)))
-    elif hdp is not None:
-        defer_head_finish(_HeadFinish(part, B, H, ns, None if one else g, None,
-                                      None, None, None, None, grads=hdp))
+        for i, (W, bias_l, img, dy, xx) in enumerate(lay):
+            dest = _grad_dest(W, bias_l, img, "tower",
+                              (lr, None if views is None else (views[i], views[n + i])))
+            dWs[i], dbs[i] = dest.dW, dest.db
+            calls.append(_Call(opnd(dy), _mrec.LAYOUT_COL, opnd(xx), _mrec.LAYOUT_COL, *W.shape, B,
+                               ph, split_k=sk, **dest.kw))
+    # --- the head's parameters: deferred, so that the launch below takes it along ---
+    head_grads = _head_param_grads(part, B, lay[-1][0].shape[0], ns, g, one, head)
+    if not calls:
+        _flush_finish()
     else:
-        f32 = dict(dtype=torch.float32, device=dev)
-        dW_h = torch.empty(1, H, **f32)
-        db_h = torch.empty(1, **f32) if head_b is not None else None
-        dws = torch.empty(ns, **f32) if ws is not None else None
-        db2 = torch.empty(1, **f32) if b2 is not None else None
-        _mrec.call("mrec_ctr_head_finish", part.data_ptr(), part.stride(0), B, H, ns,
-                   g.data_ptr(), 0, 0.0, None, None, None, None, dW_h.data_ptr(),
-                   _mrec.ptr(db_h), _mrec.ptr(dws), _mrec.ptr(db2), _mrec.stream_handle())
-    if calls and tdw:
-        _tower_dw(calls, [t[5] for t in lay], [t[6] for t in lay], [(t[3], t[4]) for t in lay], B,
-                  tdw)
-        if lr is None and dpg is None:
-            _run_all([c.with_phase(_mrec.GEMM_REDUCE) for c in calls])
+        # the partial slabs (or, without split-K, the whole GEMMs) ...
+        if tdw:
+            _tower_dw(calls, [t[3] for t in lay], [t[4] for t in lay],
+                      [tuple(t[0].shape) for t in lay], B, tdw)
         else:
-            for c in calls:
-                _defer(c)
-    elif calls:
-        launch_multi(calls)
-        if calls[0].args[8] > 1:  # split-K partial slabs: now the reductions
-            if lr is None and dpg is None:
-                # returned gradients: autograd may copy them on return, so they must
-                # be complete before this backward returns
+            launch_multi(calls)
+        # ... then the reductions of the slabs: mrec_tower_dw always leaves slabs
+        if tdw or calls[0].split_k > 1:
+            if returned:  # autograd may copy the gradients on return: complete them now
                 _run_all([c.with_phase(_mrec.GEMM_REDUCE) for c in calls])
             else:  # in-place SGD / flat DP buffer: ride in the next launches
                 for c in calls:
                     _defer(c)
-    else:
-        _flush_finish()
-    return dWs[C:], dbs[C:], (dW_h, db_h, dws, db2), (dWs[:C], dbs[:C])
-
-
-def _run_all(jobs):
-    for i in range(0, len(jobs), 4):
-        _run(jobs[i:i + 4])
+    return dWs, dbs, head_grads
 
 
 def _tower_dw(calls, dys, xins, dims, B: int, splits: int):
     """The tower's weight-gradient partial slabs by mrec_tower_dw from the
     k-fragment images (+ the deferred CTR head finish in the same launch); the
     split-K REDUCE of each call (fused SGD / flat DP buffer / returned gradient)
-    follows as usual.  Pending reductions that write what this reads run first."""
-    global _PENDING
-    reads = {t.data_ptr() for t in list(dys) + list(xins)}
-    if any(p.writes & reads for p in _PENDING):
-        _run_all(_PENDING)
-        _PENDING = []
+    follows as usual.  Pending reductions that write what this reads run first,
+    the others right after it."""
+    _flush_writers({t.data_ptr() for t in list(dys) + list(xins)})
     a = _mrec.TowerDwArgs()
     a.n_layers, a.batch, a.splits = len(calls), B, splits
     for l, c in enumerate(calls):
         a.n_out[l], a.n_in[l] = dims[l]
         a.dy_img[l], a.x_img[l] = dys[l].data_ptr(), xins[l].data_ptr()
         a.ws[l], a.ldws[l] = c.ws.data_ptr(), (dims[l][1] + 1 + 7) // 8 * 8
-    fin = _FINISH.pop(0) if _FINISH else None
+    fin = _take_finish()
     feed = take_feed_job()
-    with _timed("mrec_tower_dw"):
-        _mrec.call("mrec_tower_dw_ex", ctypes.byref(a), ctypes.byref(fin.struct) if fin else None,
-                   ctypes.byref(feed) if feed is not None else None, _mrec.stream_handle())
-    pend = _PENDING
-    _PENDING = []
-    _run_all(pend)
+    _mrec.call("mrec_tower_dw_ex", ctypes.byref(a), ctypes.byref(fin.struct) if fin else None,
+               ctypes.byref(feed) if feed is not None else None, _mrec.stream_handle())
+    _run_all(take_pending(len(_PENDING)))
 
 
 def tower_bce(x0: torch.Tensor, mlp, head: torch.nn.Linear, base: Optional[torch.Tensor],
@@ -1529,20 +1494,6 @@ class _ScoreTowerFn(torch.autograd.Function):
     the head finish, as the BCE tower's backward."""
 
     @staticmethod
-    def _args(x0, widths, imgs, bsd, hw, hb):
-        a = _mrec.TowerArgs()
-        L = len(widths) - 1
-        a.batch, a.n_layers = x0.shape[0], L
-        for l in range(L + 1):
-            a.width[l] = widths[l]
-        a.x0, a.ld_x0 = x0.data_ptr(), x0.stride(0)
-        for l in range(L):
-            a.w_fwd[l], a.w_bwd[l] = imgs[l][0].data_ptr(), imgs[l][1].data_ptr()
-            a.bias[l] = _mrec.ptr(bsd[l])
-        a.head_w, a.head_b = hw.data_ptr(), _mrec.ptr(hb)
-        return a
-
-    @staticmethod
     def forward(ctx, x0, n_layers, *params):
         L = n_layers
         Ws, bs = params[:L], params[L:2 * L]
@@ -1550,10 +1501,9 @@ class _ScoreTowerFn(torch.autograd.Function):
         B = x0.shape[0]
         widths = [Ws[0].shape[1]] + [W.shape[0] for W in Ws]
         imgs = [tower_images(W) for W in Ws]
-        f32 = lambda t: None if t is None else t.detach().float().contiguous()  # noqa: E731
-        bsd, hw, hb = [f32(b) for b in bs], f32(head_w).reshape(-1), f32(head_b)
+        bsd, hw, hb = [_f32c(b) for b in bs], _f32c(head_w).reshape(-1), _f32c(head_b)
         z = torch.empty(B, dtype=torch.float32, device=x0.device)
-        a = _ScoreTowerFn._args(x0, widths, imgs, bsd, hw, hb)
+        a = _tower_args(x0, widths, imgs, bsd, hw, hb)
         a.mode, a.z, a.ldp = _mrec.TOWER_FORWARD, z.data_ptr(), _r8(widths[L] + 1)
         _mrec.call("mrec_tower_fwd_bwd", ctypes.byref(a), _mrec.stream_handle())
         ctx.save_for_backward(x0)
@@ -1571,41 +1521,20 @@ class _ScoreTowerFn(torch.autograd.Function):
         ds = ds.detach().float().reshape(B).contiguous()
         need_w = any(ctx.needs_input_grad[2:2 + 2 * L])
         tdw = _tdw_splits(B, widths) if need_w else 0
-        if tdw:
-            kf = lambda n: torch.empty(int(_mrec.lib().mrec_kfrag_elems(B, n)), dtype=_BF16,  # noqa: E731
-                                       device=dev)
-            hs = [kf(widths[l + 1]) for l in range(L - 1)]
-            dhs = [kf(widths[l + 1]) for l in range(L)]
-            x0_img = kf(widths[0])
-        else:
-            hs = [_alloc(B, widths[l + 1], _BF16, dev) for l in range(L - 1)]
-            dhs = [_alloc(B, widths[l + 1], _BF16, dev) for l in range(L)]
-            x0_img = None
-        dx0 = None
-        if ctx.needs_input_grad[0]:
-            Kx = x0.shape[1]
-            dx0 = (_alloc(B, Kx, _BF16, dev) if _r8(Kx) == _r8(widths[0]) else
-                   torch.zeros(B, _r8(Kx), dtype=_BF16, device=dev)[:, :Kx])
+        bufs = _tower_buffers(x0, widths, tdw, ctx.needs_input_grad[0])
         H = widths[L]
-        ldp = _r8(H + 1)
-        part = torch.empty(int(_mrec.lib().mrec_ctr_head_parts(B)), ldp, dtype=torch.float32,
+        part = torch.empty(int(_mrec.lib().mrec_ctr_head_parts(B)), _r8(H + 1), dtype=torch.float32,
                            device=dev)
         bsd, hw, hb = ctx.keep
-        a = _ScoreTowerFn._args(x0, widths, ctx.imgs, bsd, hw, hb)
-        for l in range(L):
-            a.dh_out[l], a.ld_dh[l] = dhs[l].data_ptr(), dhs[l].stride(0)
-            if l < L - 1:
-                a.h_out[l], a.ld_h[l] = hs[l].data_ptr(), hs[l].stride(0)
-        a.kfrag, a.x0_img = int(bool(tdw)), _mrec.ptr(x0_img)
-        a.dx0, a.ld_dx0 = _mrec.ptr(dx0), dx0.stride(0) if dx0 is not None else 0
-        a.part, a.ldp = part.data_ptr(), ldp
+        a = _tower_args(x0, widths, ctx.imgs, bsd, hw, hb, bufs, part)
         a.mode, a.dz_in = _mrec.TOWER_GIVEN_DZ, ds.data_ptr()
         _mrec.call("mrec_tower_fwd_bwd", ctypes.byref(a), _mrec.stream_handle())
         g = grad_one(dev)
-        dWs, dbs, (dW_h, db_h, _, _), _ = _tower_param_grads(
-            widths, ctx.Ws, ctx.bs, ctx.imgs, ctx.head, B, H, 0, x0_img if tdw else x0, hs, dhs,
-            part, g, True, tdw, need_w)
-        return (dx0, None, *dWs, *dbs, dW_h, db_h)
+        xin = [bufs.x0_img if tdw else x0[:, :widths[0]]] + bufs.hs
+        dWs, dbs, (dW_h, db_h, _, _) = _tower_param_grads(
+            list(zip(ctx.Ws, ctx.bs, ctx.imgs, bufs.dhs, xin)), ctx.head, part, B, 0, g, True, tdw,
+            need_w)
+        return (bufs.dx0, None, *dWs, *dbs, dW_h, db_h)
 
 
 def score_tower(x0: torch.Tensor, mlp, head: torch.nn.Linear) -> torch.Tensor:
