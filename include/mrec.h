@@ -32,10 +32,11 @@
 extern "C" {
 #endif
 
-#define MREC_ABI_VERSION 30
+#define MREC_ABI_VERSION 31
 #define MREC_MAX_TABLES 64      /* tables per table bank / per call */
 #define MREC_BWD_MAX_BATCH 8192  /* lookups per table per plan/apply call */
 #define MREC_BWD_HASH_MAX_BATCH 4096  /* batches up to this use the hash plan */
+#define MREC_NEG_MAX_ATTEMPTS 32  /* draws per output of mrec_neg_sample before it gives up */
 
 typedef enum {
   MREC_OK = 0,
@@ -1359,6 +1360,67 @@ mrec_status mrec_ctr_head_finish(const float *part, int64_t ldp, int64_t batch, 
 mrec_status mrec_colsum(const float *s, const void *X, mrec_dtype x_dtype, int64_t ldx,
                         int64_t batch, int64_t C, float *out, float *total, int32_t update,
                         float lr, mrec_stream stream);
+
+/* ------------------------------------------------------------------------- */
+/* Ranking: pairwise losses, the positive's rank, negative sampling (ABI 31)  */
+/* ------------------------------------------------------------------------- */
+typedef enum {
+  MREC_PAIR_BPR = 0, /* softplus(neg - pos), torch's softplus: x for x > 20, else log1p(exp(x))
+                        (torchrec/loss/BPRLoss.py:15-23) */
+  MREC_PAIR_TOP1 = 1 /* sigmoid(neg - pos) + sigmoid(neg^2)  (torchrec/loss/Top1Loss.py:14-22) */
+} mrec_pair_kind;
+typedef enum { MREC_REDUCE_NONE = 0, MREC_REDUCE_MEAN = 1, MREC_REDUCE_SUM = 2 } mrec_reduction;
+
+/*
+ * Pairwise ranking losses on x [batch, 2] fp32 (row stride ld >= 2 elements; column 0
+ * the positive's score, column 1 the negative's), fp32 arithmetic.  `kind` is an
+ * mrec_pair_kind and `reduction` an mrec_reduction (int32: an unknown value is
+ * MREC_EINVAL).  Forward: out [batch] for NONE, else out [1] = the sum (SUM) or the sum
+ * / batch (MEAN) by one workgroup in a fixed order (bitwise reproducible); batch 0
+ * gives 0.  Backward: dx [batch, 2] (contiguous) = g * dl/dx, with the upstream
+ * gradient g a DEVICE pointer: g[b] for NONE, g[0] for MEAN (also scaled by 1 / batch)
+ * and SUM.  One kernel each way, no host sync.
+ */
+mrec_status mrec_pair_loss_fwd(const float *x, int64_t ld, int64_t batch, int32_t kind,
+                               int32_t reduction, float *out, mrec_stream stream);
+mrec_status mrec_pair_loss_bwd(const float *x, int64_t ld, int64_t batch, int32_t kind,
+                               int32_t reduction, const float *g, float *dx, mrec_stream stream);
+
+/*
+ * Rank of column 0 in each row of pred [rows, n] fp32 (row stride ld >= n elements):
+ *   rank[r] = 1 + #{j >= 1 : pred[r, j] > pred[r, 0]}        (int32 [rows])
+ * so a tie resolves in the positive's favour (what a stable descending sort gives);
+ * a NaN in column 0 gives rank n, a NaN in any other column never counts.  One wave
+ * per row, several rows per workgroup, no atomics.  Replaces the argsort + argwhere of
+ * IMetric.get_pos_rank (torchrec/metric/IMetric.py:17-26) on a leave-one-out
+ * candidate list whose positive is first.
+ */
+mrec_status mrec_rank_pos(const float *pred, int64_t rows, int32_t n, int64_t ld, int32_t *rank,
+                          mrec_stream stream);
+
+/*
+ * Negative sampling: out[b * n_neg + j] (int32 [batch, n_neg]) is an item of
+ * [low, high) that user uids[b] (MREC_I32 / MREC_I64) has not interacted with.  The
+ * users' items are a CSR: items[offsets[u] .. offsets[u + 1]) sorted ascending and
+ * de-duplicated, offsets int64 [n_users + 1]; a uid outside [0, n_users) has no items.
+ * With 64-bit wrapping arithmetic, G = 0x9E3779B97F4A7C15 and the splitmix64 finaliser
+ *   mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27;
+ *           z *= 0x94D049BB133111EB; z ^= z >> 31
+ * output i = b * n_neg + j has the key k = mix(mix(mix(seed + G) + step) + i), and its
+ * attempt a = 0, 1, ... draws
+ *   h = mix(k + (a + 1) * G),   item = low + (((h >> 32) * (high - low)) >> 32)
+ * (multiply-shift of the hash's high half).  A draw found in the user's items (binary
+ * search) is rejected and the next attempt drawn, MREC_NEG_MAX_ATTEMPTS at the most:
+ * then the last draw is kept and *d_unresolved (device int32, required) is incremented
+ * by one.  The result depends on (seed, step, batch, n_neg, ids) only, never on the
+ * launch geometry.  Replaces rng.integers(low, high) + the `while neg in user set`
+ * loop of SimpleDataReader.train_neg_sample (SimpleDataReader.py:280-300); numpy's
+ * own stream is not reproduced.
+ */
+mrec_status mrec_neg_sample(const void *uids, mrec_dtype uid_dtype, int64_t batch, int32_t n_neg,
+                            const int64_t *offsets, const int32_t *items, int64_t n_users,
+                            int32_t low, int32_t high, uint64_t seed, uint64_t step, int32_t *out,
+                            int32_t *d_unresolved, mrec_stream stream);
 
 #ifdef __cplusplus
 }

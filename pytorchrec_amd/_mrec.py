@@ -20,7 +20,7 @@ import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("MREC_LIB_PATH") or os.path.join(LIB_DIR, "libmrec.so")
 
-ABI_VERSION = 30
+ABI_VERSION = 31
 MAX_TABLES = 64
 BWD_MAX_BATCH = 8192
 BWD_HASH_MAX_BATCH = 4096  # batches up to this use the hash plan (fusable into a GEMM launch)
@@ -39,6 +39,10 @@ OPT_DECOUPLED_WD, OPT_NO_BIAS_CORRECTION = 1, 2
 # pooled lookups (mrec_emb_pool_fwd)
 POOL_SUM, POOL_MEAN, POOL_SQRTN = 0, 1, 2
 POOL_PAD_ZERO, POOL_PAD_NEGATIVE = 0, 1
+# ranking (mrec_pair_loss_*, mrec_neg_sample)
+PAIR_BPR, PAIR_TOP1 = 0, 1
+REDUCE_NONE, REDUCE_MEAN, REDUCE_SUM = 0, 1, 2
+NEG_MAX_ATTEMPTS = 32
 
 _STATUS_NAMES = {OK: "MREC_OK", EINVAL: "MREC_EINVAL", EOOB: "MREC_EOOB", EHIP: "MREC_EHIP",
                  ERCCL: "MREC_ERCCL", ENOSPC: "MREC_ENOSPC"}
@@ -376,6 +380,11 @@ SIGNATURES = {
                                                  _i64, _i32, _vp, _i64, _vp, _vp, _vp]),
     "mrec_shard_wire_pack": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp,
                                             _vp]),
+    "mrec_pair_loss_fwd": (ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _vp]),
+    "mrec_pair_loss_bwd": (ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "mrec_rank_pos": (ctypes.c_int, [_vp, _i64, _i32, _i64, _vp, _vp]),
+    "mrec_neg_sample": (ctypes.c_int, [_vp, ctypes.c_int, _i64, _i32, _vp, _vp, _i64, _i32, _i32,
+                                       ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp]),
     "mrec_tower_fwd_bwd": (ctypes.c_int, [ctypes.POINTER(TowerArgs), _vp]),
     "mrec_tower_image_elems": (ctypes.c_int64, [_i64, _i64, _i32]),
     "mrec_tower_weight_prep": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),

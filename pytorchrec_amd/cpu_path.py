@@ -5,12 +5,14 @@ Config C1 of BASELINE.json runs FM through the CLI on the CPU ("PyTorch CPU path
 ``embedding.py`` dispatch here: plain torch ``index_select`` gathers and autograd
 dense gradients, exactly the arithmetic ``nn.Embedding`` does on CPU
 (FunkSVD.py:47-51, IModel.py:116-125).  This module is never used for a tensor on
-a GPU — those go through libmrec or raise.
+a GPU — those go through libmrec or raise.  ``neg_sample`` is the CPU sampler of
+``sampling.NegativeSampler``: the counter hash of ``mrec_neg_sample`` in numpy.
 """
 from __future__ import annotations
 
 from typing import List, Optional
 
+import numpy as np
 import torch
 
 
@@ -83,6 +85,51 @@ def pooled_gather(bank, ids, mode: str, pad: str, out_dtype, with_w: bool):
     if with_w:
         return v, torch.stack(ws, dim=1)
     return v
+
+
+_NS_G = np.uint64(0x9E3779B97F4A7C15)
+
+
+def _mix64(z):
+    """The splitmix64 finaliser on a uint64 array (wrapping arithmetic)."""
+    z = z ^ (z >> np.uint64(30))
+    z = z * np.uint64(0xBF58476D1CE4E5B9)
+    z = z ^ (z >> np.uint64(27))
+    z = z * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def neg_sample(uids, n_neg: int, keys, n_users: int, low: int, high: int, seed: int,
+               step: int, max_attempts: int):
+    """``mrec_neg_sample`` restated in numpy uint64 (the hash is written down in
+    include/mrec.h), bit for bit: -> (int32 ``[B, n_neg]``, outputs left unresolved).
+    ``keys``: the sorted int64 array ``uid << 32 | item bits`` of the users' items."""
+    u = np.asarray(uids).astype(np.int64).reshape(-1)
+    total = u.size * n_neg
+    out = np.full(total, low, np.int32)
+    if total == 0:
+        return out.reshape(-1, n_neg), 0
+    with np.errstate(over="ignore"):
+        one = np.ones(1, np.uint64)
+        key0 = _mix64(_mix64(one * np.uint64(seed & (2 ** 64 - 1)) + _NS_G)
+                      + np.uint64(step & (2 ** 64 - 1)))
+        key = _mix64(key0 + np.arange(total, dtype=np.uint64))
+        uu = np.repeat(u, n_neg)
+        known = (uu >= 0) & (uu < n_users)
+        rng = np.uint64(high - low)
+        todo = np.arange(total)
+        for a in range(max_attempts):
+            h = _mix64(key[todo] + np.uint64(a + 1) * _NS_G)
+            item = (low + (((h >> np.uint64(32)) * rng) >> np.uint64(32)).astype(np.int64))
+            out[todo] = item.astype(np.int32)
+            probe = (uu[todo] << 32) | (item & 0xFFFFFFFF)
+            at = np.searchsorted(keys, probe)
+            taken = known[todo] & (at < keys.size)
+            taken[taken] = keys[at[taken]] == probe[taken]
+            todo = todo[taken]
+            if todo.size == 0:
+                break
+    return out.reshape(-1, n_neg), int(todo.size)
 
 
 def fm2(v: torch.Tensor) -> torch.Tensor:

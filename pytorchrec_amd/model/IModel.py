@@ -21,7 +21,14 @@ MI355X additions (documented deviations):
   * ``predict`` calls ``predict_step`` (the reference calls a missing
     ``evaluate_step`` at IModel.py:300 and cannot run).
   * metrics may be any callables ``metric(prediction, target) -> float`` with a
-    ``name``; the reference's ranking metrics are out of scope.
+    ``name``: the reference's ranking metrics (``metrics.NDCG`` / ``Hit``) and the
+    CTR metrics (``AUC`` / ``LogLoss``).  When every compiled metric is a ranking
+    metric, the model is on a GPU and ``test_step`` returns ``[U, N]`` predictions,
+    ``evaluate`` ranks each batch on the device (``mrec_rank_pos``) and copies only
+    the ranks to the host.
+  * ``set_negative_sampler``: pair-wise training draws its negatives per batch on
+    the model's device (``sampling.NegativeSampler``) when the dataset has no
+    ``train_neg_sample`` of its own (SimpleDataReader.py:280-300).
 """
 from __future__ import annotations
 
@@ -57,6 +64,7 @@ class IModel(Module, IWithArguments, ABC):
         self.compiled_loss: Optional[_Loss] = None
         self.compiled_metrics: Optional[list] = None
         self.compiled_device: Optional[torch.device] = None
+        self._neg_sampler = None  # set_negative_sampler
         self._init_weights()
         self._reset_weights()
 
@@ -415,11 +423,46 @@ class IModel(Module, IWithArguments, ABC):
             p.grad.copy_(flat[o:o + n].view_as(p.grad))
             o += n
 
+    # -- pair-wise negatives ------------------------------------------------------
+    def set_negative_sampler(self, sampler, n_neg: int = 1, uid_column=None, iid_column=None):
+        """Draw ``n_neg`` negatives per training row in ``train_step``: a batch whose
+        item ids are 1-D ``[B]`` becomes ``[B, 1 + n_neg]``, the positive first, then
+        ``sampler.sample(uids, n_neg, step)`` -- the sampled ``[B, N]`` forward branch
+        the pairwise losses expect.  ``step`` is a host counter that advances once per
+        ``train_step``, so every step draws afresh and a run is reproducible from the
+        sampler's seed.  The columns default to ``self.uid_column`` / ``self.iid_column``;
+        ``sampler=None`` turns it off."""
+        if sampler is not None and int(n_neg) < 1:
+            raise ValueError(f"n_neg must be >= 1, got {n_neg}")
+        ucol = uid_column if uid_column is not None else getattr(self, "uid_column", None)
+        icol = iid_column if iid_column is not None else getattr(self, "iid_column", None)
+        if sampler is not None and (ucol is None or icol is None):
+            raise ValueError("the model has no uid_column / iid_column: pass them")
+        self._neg_sampler = sampler
+        self._neg_columns = (ucol, icol)
+        self._neg_n = int(n_neg)
+        self._neg_step = 0
+
+    def _with_negatives(self, data: Dict) -> Dict:
+        ucol, icol = self._neg_columns
+        step = self._neg_step
+        self._neg_step += 1
+        pos = data[icol.feature_name]
+        if pos.dim() != 1:
+            return data  # the dataset sampled its own candidates
+        neg = self._neg_sampler.sample(ucol.get_feature_ids(data), self._neg_n, step=step)
+        data = dict(data)
+        data[icol.feature_name] = torch.cat(
+            [pos.reshape(-1, 1), neg.to(device=pos.device, dtype=pos.dtype)], dim=1)
+        return data
+
     # -- steps ------------------------------------------------------------------
     def train_step(self, data: Dict):
         self.train()
         self._weights_version += 1
         data = tensor_to_device(data, self.compiled_device)
+        if self._neg_sampler is not None:
+            data = self._with_negatives(data)
         fused = self._fused_loss_fn()
         if fused is not None:
             # output layer + loss (+ their gradients) in one kernel; same math as
@@ -490,9 +533,14 @@ class IModel(Module, IWithArguments, ABC):
         self._assert_compile_was_called()
         self.stop_training = False
         self.history = []
+        pair_wise = (train_mode is not None
+                     and str(getattr(train_mode, "value", train_mode)) == "pair_wise")
+        own_negatives = hasattr(dataset, "train_neg_sample")
+        if pair_wise and not own_negatives and self._neg_sampler is None:
+            raise ValueError("train_mode='pair_wise' needs negatives: a dataset with "
+                             "train_neg_sample(), or model.set_negative_sampler(...)")
         for epoch in range(epochs):
-            if hasattr(dataset, "train_neg_sample") and train_mode is not None and \
-                    str(getattr(train_mode, "value", train_mode)) == "pair_wise":
+            if pair_wise and own_negatives:  # the dataset's own resampling wins
                 dataset.train_neg_sample()
             logs = {}
             for data in self._loader(dataset, batch_size, shuffle, workers, drop_last):
@@ -514,11 +562,24 @@ class IModel(Module, IWithArguments, ABC):
     def evaluate(self, dataset, batch_size: int, verbose: int = 1, callbacks=None, workers: int = 0):
         self._assert_compile_was_called()
         self.flush_embedding_optimizers()
-        preds, targets = [], []
+        from pytorchrec_amd.metrics import RankingMetric, rank_pos_device
+        # every metric a function of the positives' ranks, on a GPU: rank each [U, N]
+        # batch on the device and copy the ranks once; the predictions stay there
+        on_device = (bool(self.compiled_metrics) and self.compiled_device.type == "cuda"
+                     and all(isinstance(m, RankingMetric) for m in self.compiled_metrics))
+        preds, targets, dev_ranks = [], [], []
         for data in self._loader(dataset, batch_size, workers=workers):
             p, t = self.test_step(data)
+            if on_device and p.dim() == 2 and p.is_cuda:
+                dev_ranks.append(rank_pos_device(p))
+                continue
             preds.append(p.detach().float().cpu().numpy())
             targets.append(t.detach().float().cpu().numpy())
+        if dev_ranks:
+            if preds:
+                raise ValueError("evaluate: the batches mix 1-D and [U, N] predictions")
+            ranks = torch.cat(dev_ranks).cpu().numpy().astype(np.int64)
+            return {m.name: float(m.fast_calc(ranks)) for m in self.compiled_metrics}
         predictions = np.concatenate(preds) if preds else np.zeros(0)
         target = np.concatenate(targets) if targets else np.zeros(0)
         return {getattr(m, "name", type(m).__name__): float(m(predictions, target))
