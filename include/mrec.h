@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MREC_ABI_VERSION 31
+#define MREC_ABI_VERSION 32
 #define MREC_MAX_TABLES 64      /* tables per table bank / per call */
 #define MREC_BWD_MAX_BATCH 8192  /* lookups per table per plan/apply call */
 #define MREC_BWD_HASH_MAX_BATCH 4096  /* batches up to this use the hash plan */
@@ -1421,6 +1421,82 @@ mrec_status mrec_neg_sample(const void *uids, mrec_dtype uid_dtype, int64_t batc
                             const int64_t *offsets, const int32_t *items, int64_t n_users,
                             int32_t low, int32_t high, uint64_t seed, uint64_t step, int32_t *out,
                             int32_t *d_unresolved, mrec_stream stream);
+
+/* ------------------------------------------------------------------------- */
+/* SASRec encoder, fused per sample (ABI 32; csrc/sasrec.hip)                  */
+/* ------------------------------------------------------------------------- */
+/*
+ * The whole SASRec encoder (torchrec/model/SASRec.py:83-110) in one launch each way.
+ * Per sample b, with valid_j = his[b, j] > 0 or j == 0:
+ *   X      = bf16(rows[b L + j] + pos[(his_len[b] - j)]) at valid j, a zero row elsewhere
+ *   num_layers x the ONE shared block:
+ *     Q = X wq^T, K = X wk^T, A = softmax_k(D^-0.5 Q K^T) over valid keys (shifted by
+ *     the row's own maximum), X <- bf16(LayerNorm(X + relu(A K w1^T + b1) w2^T + b2))
+ *   v[b]   = sum_{valid j} X_j / his_len[b]                                  (fp32)
+ * bf16 MFMA operands, fp32 accumulation / softmax / LayerNorm.  One description for
+ * both directions; the forward ignores the backward's fields.
+ *   rows    gathered item rows [batch L] bf16 (row stride ld_rows, a multiple of 8;
+ *           16-B aligned); his [batch, L] (ld_his), his_len [batch]: int32;
+ *   pos     position table [pos_rows, D] fp32 (ld_pos); a valid position whose id
+ *           his_len - j falls outside [0, pos_rows) contributes no position row and
+ *           sets *d_oob_flag = 1 (NULL: not reported), the bank's convention;
+ *   wq, wk, w1, w2 [D, D] (ld_*), b1, b2, gamma, beta [D]: fp32 masters, nn.Linear
+ *           layout, converted to bf16 in the kernel;
+ *   hs      [num_layers, batch, L, D] bf16, contiguous: the layer outputs, written by
+ *           the forward and read by the backward, which recomputes everything else;
+ *   v       [batch, D] fp32 (forward);
+ *   dv      [batch, D] fp32; d_rows (row stride ld_drows) the rows' bf16 gradient,
+ *           bitwise zero at invalid positions; part [parts][mrec_sasrec_param_count]
+ *           fp32 per-workgroup partials of every dense gradient, flat
+ *           [dwq | dwk | dw1 | dw2 | db1 | db2 | dgamma | dbeta | dpos], summed over the
+ *           workgroup's samples and the layers (parts = mrec_sasrec_parts(batch)).
+ * mrec_sasrec_wgrad sums `count` columns of the partials in workgroup order into grads
+ * (bit-reproducible).  Compiled shapes (mrec_sasrec_supported): D in {16, 32, 64},
+ * 1 <= L <= 64.  Stream-ordered, no allocation; anything else is MREC_EINVAL.
+ */
+typedef struct {
+  const void *rows;
+  int64_t ld_rows;
+  const int32_t *his;
+  int64_t ld_his;
+  const int32_t *his_len;
+  const float *pos;
+  int64_t ld_pos;
+  int32_t pos_rows;
+  const float *wq;
+  int64_t ld_wq;
+  const float *wk;
+  int64_t ld_wk;
+  const float *w1;
+  int64_t ld_w1;
+  const float *b1;
+  const float *w2;
+  int64_t ld_w2;
+  const float *b2;
+  const float *gamma;
+  const float *beta;
+  float eps;
+  int32_t num_layers;
+  int64_t batch;
+  int32_t L;
+  int32_t D;
+  void *hs;
+  float *v;
+  int32_t *d_oob_flag;
+  const float *dv;
+  void *d_rows;
+  int64_t ld_drows;
+  float *part;
+  int64_t parts;
+} mrec_sasrec_args;
+
+int32_t mrec_sasrec_supported(int32_t D, int32_t L);
+int64_t mrec_sasrec_parts(int64_t batch);
+int64_t mrec_sasrec_param_count(int32_t D, int32_t pos_rows);
+mrec_status mrec_sasrec_fwd(const mrec_sasrec_args *args, mrec_stream stream);
+mrec_status mrec_sasrec_bwd(const mrec_sasrec_args *args, mrec_stream stream);
+mrec_status mrec_sasrec_wgrad(const float *part, int64_t parts, int64_t count, float *grads,
+                              mrec_stream stream);
 
 #ifdef __cplusplus
 }

@@ -20,7 +20,7 @@ import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("MREC_LIB_PATH") or os.path.join(LIB_DIR, "libmrec.so")
 
-ABI_VERSION = 31
+ABI_VERSION = 32
 MAX_TABLES = 64
 BWD_MAX_BATCH = 8192
 BWD_HASH_MAX_BATCH = 4096  # batches up to this use the hash plan (fusable into a GEMM launch)
@@ -212,6 +212,24 @@ class FeedJob(ctypes.Structure):
                 ("d_state", ctypes.c_void_p), ("widen_bytes", ctypes.c_int64)]
 
 
+class SasrecArgs(ctypes.Structure):
+    """mrec_sasrec_args (include/mrec.h, ABI 32): one description for both directions."""
+    _fields_ = [("rows", ctypes.c_void_p), ("ld_rows", ctypes.c_int64),
+                ("his", ctypes.c_void_p), ("ld_his", ctypes.c_int64),
+                ("his_len", ctypes.c_void_p),
+                ("pos", ctypes.c_void_p), ("ld_pos", ctypes.c_int64), ("pos_rows", ctypes.c_int32),
+                ("wq", ctypes.c_void_p), ("ld_wq", ctypes.c_int64),
+                ("wk", ctypes.c_void_p), ("ld_wk", ctypes.c_int64),
+                ("w1", ctypes.c_void_p), ("ld_w1", ctypes.c_int64), ("b1", ctypes.c_void_p),
+                ("w2", ctypes.c_void_p), ("ld_w2", ctypes.c_int64), ("b2", ctypes.c_void_p),
+                ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p),
+                ("eps", ctypes.c_float), ("num_layers", ctypes.c_int32),
+                ("batch", ctypes.c_int64), ("L", ctypes.c_int32), ("D", ctypes.c_int32),
+                ("hs", ctypes.c_void_p), ("v", ctypes.c_void_p), ("d_oob_flag", ctypes.c_void_p),
+                ("dv", ctypes.c_void_p), ("d_rows", ctypes.c_void_p), ("ld_drows", ctypes.c_int64),
+                ("part", ctypes.c_void_p), ("parts", ctypes.c_int64)]
+
+
 LAYOUT_ROW, LAYOUT_COL = 0, 1
 ACT_NONE, ACT_RELU = 0, 1
 
@@ -385,6 +403,12 @@ SIGNATURES = {
     "mrec_rank_pos": (ctypes.c_int, [_vp, _i64, _i32, _i64, _vp, _vp]),
     "mrec_neg_sample": (ctypes.c_int, [_vp, ctypes.c_int, _i64, _i32, _vp, _vp, _i64, _i32, _i32,
                                        ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp]),
+    "mrec_sasrec_supported": (ctypes.c_int32, [_i32, _i32]),
+    "mrec_sasrec_parts": (ctypes.c_int64, [_i64]),
+    "mrec_sasrec_param_count": (ctypes.c_int64, [_i32, _i32]),
+    "mrec_sasrec_fwd": (ctypes.c_int, [ctypes.POINTER(SasrecArgs), _vp]),
+    "mrec_sasrec_bwd": (ctypes.c_int, [ctypes.POINTER(SasrecArgs), _vp]),
+    "mrec_sasrec_wgrad": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "mrec_tower_fwd_bwd": (ctypes.c_int, [ctypes.POINTER(TowerArgs), _vp]),
     "mrec_tower_image_elems": (ctypes.c_int64, [_i64, _i64, _i32]),
     "mrec_tower_weight_prep": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),

@@ -4,9 +4,12 @@ Config C1 of BASELINE.json runs FM through the CLI on the CPU ("PyTorch CPU path
 (plumbing, no GPU)").  For a bank whose weight lives on the CPU, the ops in
 ``embedding.py`` dispatch here: plain torch ``index_select`` gathers and autograd
 dense gradients, exactly the arithmetic ``nn.Embedding`` does on CPU
-(FunkSVD.py:47-51, IModel.py:116-125).  This module is never used for a tensor on
-a GPU — those go through libmrec or raise.  ``neg_sample`` is the CPU sampler of
-``sampling.NegativeSampler``: the counter hash of ``mrec_neg_sample`` in numpy.
+(FunkSVD.py:47-51, IModel.py:116-125).  The bank ops of this module are never used
+for a tensor on a GPU — those go through libmrec or raise.  ``neg_sample`` is the CPU
+sampler of ``sampling.NegativeSampler``: the counter hash of ``mrec_neg_sample`` in
+numpy.  ``sasrec_encode`` is the SASRec encoder in torch ops: the CPU path, and on a GPU
+the layered path for the shapes and modes the fused kernels do not cover
+(``dense.sasrec_encode`` decides).
 """
 from __future__ import annotations
 
@@ -130,6 +133,59 @@ def neg_sample(uids, n_neg: int, keys, n_users: int, low: int, high: int, seed: 
             if todo.size == 0:
                 break
     return out.reshape(-1, n_neg), int(todo.size)
+
+
+def bf16_round(t: torch.Tensor) -> torch.Tensor:
+    """fp32 -> nearest bf16 -> fp32, with the identity as its gradient."""
+    return t + (t.to(torch.bfloat16).float() - t).detach()
+
+
+def sasrec_positions(his: torch.Tensor, his_len: torch.Tensor):
+    """(valid [B, L] bool, position ids [B, L] int64) of a padded history:
+    valid_j = his_j > 0 with valid_0 forced (utils.py:5-10), pos_j = (his_len - j) valid_j
+    (utils.py:13-17)."""
+    valid = his > 0
+    valid[:, 0] = True
+    j = torch.arange(his.shape[1], device=his.device)
+    return valid, (his_len.long().unsqueeze(-1) - j) * valid.long()
+
+
+def sasrec_encode(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor, pos_w, wq, wk, w1,
+                  b1, w2, b2, gamma, beta, eps: float, num_layers: int, dropout: float = 0.0,
+                  training: bool = False, rnd=None) -> torch.Tensor:
+    """The SASRec encoder (SASRec.py:83-110) in fp32 torch ops; autograd is its backward.
+
+    rows [B, L, D] item rows of the padded history, his [B, L] ids, his_len [B] ->
+    v [B, D] = sum_{valid j} X_j / his_len after ``num_layers`` passes of the ONE shared
+    block  Q = X Wq^T, K = X Wk^T, A = softmax_k(D^-0.5 Q K^T) over valid keys,
+    X <- LayerNorm(X + dropout(relu(A K W1^T + b1) W2^T + b2)).  The softmax shift is the
+    row maximum (the reference's global ``attention.max()`` is the same softmax on paper
+    and NaN when the global maximum sits far above every valid score of a row).
+
+    ``rnd`` rounds X, the four weight matrices and every matmul operand (identity
+    here; ``bf16_round`` on a GPU, where this is the layered path whose rounding
+    points are the fused kernel's).  A position id outside the table is IndexError."""
+    r = rnd if rnd is not None else (lambda t: t)
+    B, L, D = rows.shape
+    valid, pos = sasrec_positions(his, his_len)
+    if pos.numel() and (int(pos.min()) < 0 or int(pos.max()) >= pos_w.shape[0]):
+        raise IndexError("index out of range in self")
+    x = r(rows.float() + pos_w.float().index_select(0, pos.reshape(-1)).reshape(B, L, D))
+    wq, wk, w1, w2 = (r(w.float()) for w in (wq, wk, w1, w2))
+    key_mask = ~valid.unsqueeze(1)  # [B, 1, L]: every query row sees the valid keys
+    scale = D ** -0.5
+    for _ in range(num_layers):
+        q, k = r(x @ wq.t()), r(x @ wk.t())
+        s = torch.bmm(q, k.transpose(1, 2)) * scale
+        a = torch.softmax(s.masked_fill(key_mask, float("-inf")), dim=-1)
+        c = r(torch.bmm(r(a), k))
+        f = r(torch.relu(c @ w1.t() + b1.float()))
+        g = f @ w2.t() + b2.float()
+        if training and dropout > 0:
+            g = torch.nn.functional.dropout(g, p=dropout, training=True)
+        x = r(torch.nn.functional.layer_norm(x + g, (D,), gamma.float(), beta.float(), eps))
+    v = (x * valid.unsqueeze(-1).float()).sum(1)
+    return v / his_len.unsqueeze(-1).float()
 
 
 def fm2(v: torch.Tensor) -> torch.Tensor:

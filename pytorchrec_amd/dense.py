@@ -1,4 +1,5 @@
-"""Dense-tower ops: Linear(+bias)(+ReLU), DCN-v2 cross, DIN attention pooling.
+"""Dense-tower ops: Linear(+bias)(+ReLU), DCN-v2 cross, DIN attention pooling, the
+SASRec encoder.
 
 One seam for the model code.  On a GPU they run on libmrec's MFMA bf16 GEMM
 (``mrec_gemm``: fp32 accumulation, bias / ReLU / DCN epilogues fused, the fp32
@@ -949,6 +950,117 @@ def din_attention_top(q: torch.Tensor, k: torch.Tensor, his: torch.Tensor, att_m
     feat = _DinFeatFn.apply(q, k, st, L)
     s = _din_scores(feat, att_mlp, att_out)
     return _DinPoolFn.apply(s, q, k, his, st, L)
+
+
+# the fused SASRec encoder (mrec_sasrec_*, sasrec.hip) is the default for the compiled
+# shapes; False selects the layered path (the parity tests set it)
+SASREC_FUSED = True
+
+
+def sasrec_supported(D: int, L: int, num_layers: int = 1, dropout: float = 0.0,
+                     training: bool = False) -> bool:
+    """True when the fused encoder covers this block: a compiled (D, L), at least one
+    layer and no active dropout.  Decided from the shape alone; never an error."""
+    if num_layers < 1 or (training and dropout > 0):
+        return False
+    return bool(_mrec.lib().mrec_sasrec_supported(int(D), int(L)))
+
+
+def _sasrec_params(model):
+    ln = model.layer_norm
+    return (model.p_embeddings.weight, model.Q.weight, model.K.weight, model.W1.weight,
+            model.W1.bias, model.W2.weight, model.W2.bias, ln.weight, ln.bias)
+
+
+class _SasrecFn(torch.autograd.Function):
+    """The whole SASRec encoder over the gathered history rows [B, L, D]: one forward
+    launch (every layer -> v [B, D], the layer outputs saved), one backward launch
+    (the rows' bf16 gradient + per-workgroup partials of the nine dense gradients) and
+    the partials' fixed-order sum."""
+
+    @staticmethod
+    def forward(ctx, rows, his, his_len, check: bool, eps: float, num_layers: int, pos, wq, wk,
+                w1, b1, w2, b2, gamma, beta):
+        B, L, D = rows.shape
+        dev = rows.device
+        rows2 = _bf16_rows(rows.reshape(B * L, D))
+        his = his.to(torch.int32)
+        if his.stride(1) != 1:
+            his = his.contiguous()
+        his_len = his_len.reshape(-1).to(torch.int32).contiguous()
+        ws = [_weight_f32(pos), _weight_f32(wq), _weight_f32(wk), _weight_f32(w1), _f32c(b1),
+              _weight_f32(w2), _f32c(b2), _f32c(gamma), _f32c(beta)]
+        hs = torch.empty(num_layers, B, L, D, dtype=_BF16, device=dev)
+        v = torch.empty(B, D, dtype=torch.float32, device=dev)
+        flag = torch.zeros(1, dtype=torch.int32, device=dev) if check else None
+        a = _mrec.SasrecArgs(
+            rows2.data_ptr(), rows2.stride(0), his.data_ptr(), his.stride(0), his_len.data_ptr(),
+            ws[0].data_ptr(), ws[0].stride(0), ws[0].shape[0], ws[1].data_ptr(), ws[1].stride(0),
+            ws[2].data_ptr(), ws[2].stride(0), ws[3].data_ptr(), ws[3].stride(0),
+            ws[4].data_ptr(), ws[5].data_ptr(), ws[5].stride(0), ws[6].data_ptr(),
+            ws[7].data_ptr(), ws[8].data_ptr(), float(eps), int(num_layers), B, L, D,
+            hs.data_ptr(), v.data_ptr(), _mrec.ptr(flag), None, None, 0, None, 0)
+        if B:
+            _mrec.call("mrec_sasrec_fwd", ctypes.byref(a), _mrec.stream_handle())
+        if flag is not None and int(flag.item()) != 0:
+            raise IndexError("index out of range in self")
+        a.d_oob_flag = None
+        ctx.args, ctx.keep = a, (rows2, his, his_len, ws, hs)
+        ctx.params = (pos, wq, wk, w1, b1, w2, b2, gamma, beta)
+        return v
+
+    @staticmethod
+    def backward(ctx, dv):
+        a, (rows2, his, his_len, ws, hs) = ctx.args, ctx.keep
+        params = ctx.params
+        B, L, D = int(a.batch), int(a.L), int(a.D)
+        dev = rows2.device
+        dv = dv.detach().float().contiguous()
+        d_rows = torch.empty(B * L, D, dtype=_BF16, device=dev)
+        lib = _mrec.lib()
+        parts = int(lib.mrec_sasrec_parts(B))
+        P = int(lib.mrec_sasrec_param_count(D, ws[0].shape[0]))
+        part = torch.empty(parts, P, dtype=torch.float32, device=dev)
+        g = torch.zeros(P, dtype=torch.float32, device=dev)
+        a.dv, a.d_rows, a.ld_drows = dv.data_ptr(), d_rows.data_ptr(), d_rows.stride(0)
+        a.part, a.parts = part.data_ptr(), parts
+        st = _mrec.stream_handle()
+        if B:
+            _mrec.call("mrec_sasrec_bwd", ctypes.byref(a), st)
+            _mrec.call("mrec_sasrec_wgrad", part.data_ptr(), parts, P, g.data_ptr(), st)
+        ctx.args = ctx.keep = None
+        sizes = [D * D] * 4 + [D] * 4 + [ws[0].shape[0] * D]
+        gq, gk, g1, g2, gb1, gb2, gga, gbe, gpos = torch.split(g, sizes)
+        grads = [t.view_as(p) for t, p in
+                 zip((gpos, gq, gk, g1, gb1, g2, gb2, gga, gbe), params)]
+        head = (d_rows.reshape(B, L, D), None, None, None, None, None)
+        dpg = dp_grads(*params)
+        if dpg is not None:  # data parallel: into the flat buffer IModel all-reduces
+            for dst, src in zip(dpg, grads):
+                dst.copy_(src.view_as(dst))
+            return head + (None,) * 9
+        return head + tuple(grads)
+
+
+def sasrec_encode(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor,
+                  model) -> torch.Tensor:
+    """v [B, D] (fp32) of the SASRec encoder over the gathered history rows [B, L, D]
+    with ``model``'s shared block (p_embeddings, Q, K, W1, W2, layer_norm, num_layers,
+    dropout).  On a GPU the fused kernels when they cover the shape; else, on the CPU
+    and when dropout is active, the layered path: the same arithmetic as torch ops
+    (``cpu_path.sasrec_encode``), rounding to bf16 on a GPU where the kernel does."""
+    from pytorchrec_amd import cpu_path
+    B, L, D = rows.shape
+    params = _sasrec_params(model)
+    eps, nl = model.layer_norm.eps, model.num_layers
+    if (rows.is_cuda and SASREC_FUSED
+            and sasrec_supported(D, L, nl, model.dropout, model.training)
+            and all(p.dtype == torch.float32 for p in params)):
+        check = bool(getattr(model.i_embeddings, "check_ids", True))
+        return _SasrecFn.apply(rows, his, his_len, check, eps, nl, *params)
+    return cpu_path.sasrec_encode(rows, his, his_len, *params, eps, nl, dropout=model.dropout,
+                                  training=model.training,
+                                  rnd=cpu_path.bf16_round if rows.is_cuda else None)
 
 
 def colsum(s: torch.Tensor, X: Optional[torch.Tensor], want_total: bool = True, *,

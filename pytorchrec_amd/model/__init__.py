@@ -5,4 +5,5 @@ from pytorchrec_amd.model.DCNv2 import DCNv2
 from pytorchrec_amd.model.DIN import DIN
 from pytorchrec_amd.model.FunkSVD import FunkSVD
 from pytorchrec_amd.model.SVDPP import SVDPP
+from pytorchrec_amd.model.SASRec import SASRec
 from pytorchrec_amd.model.models import get_model_type, model_name_list

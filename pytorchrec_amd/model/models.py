@@ -6,11 +6,13 @@ from pytorchrec_amd.model.DeepFM import FM, DeepFM
 from pytorchrec_amd.model.DIN import DIN
 from pytorchrec_amd.model.FunkSVD import FunkSVD
 from pytorchrec_amd.model.IModel import IModel
+from pytorchrec_amd.model.SASRec import SASRec
 from pytorchrec_amd.model.SVDPP import SVDPP
 
 _model_classes: Dict[str, Type[IModel]] = {
     "funksvd": FunkSVD,
     "svdpp": SVDPP,
+    "sasrec": SASRec,
     "fm": FM,
     "deepfm": DeepFM,
     "dcnv2": DCNv2,
