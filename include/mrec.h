@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MREC_ABI_VERSION 32
+#define MREC_ABI_VERSION 33
 #define MREC_MAX_TABLES 64      /* tables per table bank / per call */
 #define MREC_BWD_MAX_BATCH 8192  /* lookups per table per plan/apply call */
 #define MREC_BWD_HASH_MAX_BATCH 4096  /* batches up to this use the hash plan */
@@ -1497,6 +1497,73 @@ mrec_status mrec_sasrec_fwd(const mrec_sasrec_args *args, mrec_stream stream);
 mrec_status mrec_sasrec_bwd(const mrec_sasrec_args *args, mrec_stream stream);
 mrec_status mrec_sasrec_wgrad(const float *part, int64_t parts, int64_t count, float *grads,
                               mrec_stream stream);
+
+/* ------------------------------------------------------------------------- */
+/* GRU4Rec session encoder, the whole recurrence per launch (ABI 33; csrc/gru.hip) */
+/* ------------------------------------------------------------------------- */
+/*
+ * The GRU of torchrec/model/GRU4Rec.py:51-56 (nn.GRU over the packed history, one
+ * layer, h_-1 = 0) in one launch each way.  Per sample b, for t = 0 .. his_len[b] - 1:
+ *   x_t = rows[b L + t]
+ *   r_t = sigmoid(W_ir x_t + b_ir + W_hr h_{t-1} + b_hr)
+ *   z_t = sigmoid(W_iz x_t + b_iz + W_hz h_{t-1} + b_hz)
+ *   n_t = tanh(W_in x_t + b_in + r_t (W_hn h_{t-1} + b_hn))
+ *   h_t = (1 - z_t) n_t + z_t h_{t-1};      h_last[b] = h_{his_len[b] - 1}
+ * x, the two weight matrices and h as a product's operand are rounded to bf16, every
+ * product accumulates in fp32, the gate math and the carried h are fp32.  A position is
+ * live iff t < his_len[b]; rows at other positions are never read.
+ *   rows    bf16 gathered rows [batch * L], row stride ld_rows elements (16-byte aligned
+ *           rows: ld_rows a multiple of 8);
+ *   his_len int32 [batch]; a length outside 1 .. L sets *d_oob_flag (may be NULL) and is
+ *           clamped into 0 .. L (0: h_last = 0), nothing is read out of bounds;
+ *   order   int32 [batch] or NULL: tile slot -> sample, a permutation that puts samples of
+ *           similar length into the same 16-sample tile (speed only: a sample's bits do
+ *           not depend on it); an entry outside the batch sets the flag and is skipped;
+ *   w_ih [3H, E], w_hh [3H, H] (row strides ld_ih, ld_hh), b_ih, b_hh [3H]: the fp32
+ *           masters in nn.GRU's layout, gate order r, z, n;
+ *   hs      [batch, L, H] fp32, the hidden sequence as the forward carried it, written at
+ *           live positions (forward) and read by the backward, which recomputes the gates;
+ *   h_last  [batch, H] fp32 (forward);
+ *   dh_last [batch, H] fp32; d_rows (row stride ld_drows) the rows' bf16 gradient,
+ *           bitwise zero at t >= his_len; part [parts][mrec_gru_param_count] fp32
+ *           per-workgroup partials of the dense gradients, flat
+ *           [dW_ih | dW_hh | db_ih | db_hh] (parts = mrec_gru_parts(batch)), to be summed
+ *           in workgroup order by mrec_sasrec_wgrad (bit-reproducible).
+ * Compiled shapes (mrec_gru_supported): E, H in {16, 32, 64}, 1 <= L <= 64.  A workgroup
+ * takes mrec_gru_tile() samples at a time.  Stream-ordered, no allocation; anything
+ * else is MREC_EINVAL before any device work.
+ */
+typedef struct {
+  const void *rows;
+  int64_t ld_rows;
+  const int32_t *his_len;
+  const int32_t *order;
+  const float *w_ih;
+  int64_t ld_ih;
+  const float *w_hh;
+  int64_t ld_hh;
+  const float *b_ih;
+  const float *b_hh;
+  int32_t E;
+  int32_t H;
+  int32_t L;
+  int64_t batch;
+  void *hs;
+  float *h_last;
+  int32_t *d_oob_flag;
+  const float *dh_last;
+  void *d_rows;
+  int64_t ld_drows;
+  float *part;
+  int64_t parts;
+} mrec_gru_args;
+
+int32_t mrec_gru_supported(int32_t E, int32_t H, int32_t L);
+int32_t mrec_gru_tile(void);
+int64_t mrec_gru_parts(int64_t batch);
+int64_t mrec_gru_param_count(int32_t E, int32_t H);
+mrec_status mrec_gru_fwd(const mrec_gru_args *args, mrec_stream stream);
+mrec_status mrec_gru_bwd(const mrec_gru_args *args, mrec_stream stream);
 
 #ifdef __cplusplus
 }

@@ -20,7 +20,7 @@ import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("MREC_LIB_PATH") or os.path.join(LIB_DIR, "libmrec.so")
 
-ABI_VERSION = 32
+ABI_VERSION = 33
 MAX_TABLES = 64
 BWD_MAX_BATCH = 8192
 BWD_HASH_MAX_BATCH = 4096  # batches up to this use the hash plan (fusable into a GEMM launch)
@@ -230,6 +230,21 @@ class SasrecArgs(ctypes.Structure):
                 ("part", ctypes.c_void_p), ("parts", ctypes.c_int64)]
 
 
+class GruArgs(ctypes.Structure):
+    """mrec_gru_args (include/mrec.h, ABI 33): one description for both directions."""
+    _fields_ = [("rows", ctypes.c_void_p), ("ld_rows", ctypes.c_int64),
+                ("his_len", ctypes.c_void_p), ("order", ctypes.c_void_p),
+                ("w_ih", ctypes.c_void_p), ("ld_ih", ctypes.c_int64),
+                ("w_hh", ctypes.c_void_p), ("ld_hh", ctypes.c_int64),
+                ("b_ih", ctypes.c_void_p), ("b_hh", ctypes.c_void_p),
+                ("E", ctypes.c_int32), ("H", ctypes.c_int32), ("L", ctypes.c_int32),
+                ("batch", ctypes.c_int64),
+                ("hs", ctypes.c_void_p), ("h_last", ctypes.c_void_p),
+                ("d_oob_flag", ctypes.c_void_p), ("dh_last", ctypes.c_void_p),
+                ("d_rows", ctypes.c_void_p), ("ld_drows", ctypes.c_int64),
+                ("part", ctypes.c_void_p), ("parts", ctypes.c_int64)]
+
+
 LAYOUT_ROW, LAYOUT_COL = 0, 1
 ACT_NONE, ACT_RELU = 0, 1
 
@@ -409,6 +424,12 @@ SIGNATURES = {
     "mrec_sasrec_fwd": (ctypes.c_int, [ctypes.POINTER(SasrecArgs), _vp]),
     "mrec_sasrec_bwd": (ctypes.c_int, [ctypes.POINTER(SasrecArgs), _vp]),
     "mrec_sasrec_wgrad": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp]),
+    "mrec_gru_supported": (ctypes.c_int32, [_i32, _i32, _i32]),
+    "mrec_gru_tile": (ctypes.c_int32, []),
+    "mrec_gru_parts": (ctypes.c_int64, [_i64]),
+    "mrec_gru_param_count": (ctypes.c_int64, [_i32, _i32]),
+    "mrec_gru_fwd": (ctypes.c_int, [ctypes.POINTER(GruArgs), _vp]),
+    "mrec_gru_bwd": (ctypes.c_int, [ctypes.POINTER(GruArgs), _vp]),
     "mrec_tower_fwd_bwd": (ctypes.c_int, [ctypes.POINTER(TowerArgs), _vp]),
     "mrec_tower_image_elems": (ctypes.c_int64, [_i64, _i64, _i32]),
     "mrec_tower_weight_prep": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),

@@ -9,7 +9,8 @@ for a tensor on a GPU — those go through libmrec or raise.  ``neg_sample`` is 
 sampler of ``sampling.NegativeSampler``: the counter hash of ``mrec_neg_sample`` in
 numpy.  ``sasrec_encode`` is the SASRec encoder in torch ops: the CPU path, and on a GPU
 the layered path for the shapes and modes the fused kernels do not cover
-(``dense.sasrec_encode`` decides).
+(``dense.sasrec_encode`` decides); ``gru_encode`` is the same for the GRU4Rec recurrence
+(``dense.gru_encode`` decides).
 """
 from __future__ import annotations
 
@@ -186,6 +187,43 @@ def sasrec_encode(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor, 
         x = r(torch.nn.functional.layer_norm(x + g, (D,), gamma.float(), beta.float(), eps))
     v = (x * valid.unsqueeze(-1).float()).sum(1)
     return v / his_len.unsqueeze(-1).float()
+
+
+def gru_encode(rows: torch.Tensor, his_len: torch.Tensor, w_ih, w_hh, b_ih, b_hh,
+               rnd=None, check: bool = True) -> torch.Tensor:
+    """The GRU4Rec encoder (GRU4Rec.py:51-56: one-layer nn.GRU over the packed history,
+    h_-1 = 0) in fp32 torch ops; autograd is its backward.
+
+    rows [B, L, E] item rows of the history, his_len [B] in 1..L -> h_{his_len - 1} [B, H]:
+        r, z = sigmoid(W_i{r,z} x_t + b_i{r,z} + W_h{r,z} h + b_h{r,z})
+        n    = tanh(W_in x_t + b_in + r (W_hn h + b_hn));   h <- (1 - z) n + z h
+    Sample b runs exactly his_len[b] steps (a ``where`` past the length freezes h), which
+    is all the reference's sort / pack / unsort does; the rows at t >= his_len never
+    matter.  A length outside 1..L is IndexError (the reference cannot pack it); with
+    ``check`` off it is not looked at: 0 gives h = 0, more than L runs L steps.
+
+    ``rnd`` rounds x, the two weight matrices and h as a matmul operand (identity here;
+    ``bf16_round`` on a GPU, where this is the layered path whose rounding points are the
+    fused kernel's)."""
+    r_ = rnd if rnd is not None else (lambda t: t)
+    B, L, E = rows.shape
+    H = w_hh.shape[1]
+    lens = his_len.reshape(-1).long()
+    if check and B and (int(lens.min()) < 1 or int(lens.max()) > L):
+        raise IndexError("index out of range in self")
+    x = r_(rows.float())
+    wi, wh = r_(w_ih.float()), r_(w_hh.float())
+    gx = x @ wi.t() + b_ih.float()  # [B, L, 3H]: the input products do not depend on h
+    h = torch.zeros(B, H, dtype=torch.float32, device=rows.device)
+    for t in range(L):
+        gh = r_(h) @ wh.t() + b_hh.float()
+        xr, xz, xn = gx[:, t].split(H, dim=1)
+        hr, hz, hn = gh.split(H, dim=1)
+        r = torch.sigmoid(xr + hr)
+        z = torch.sigmoid(xz + hz)
+        n = torch.tanh(xn + r * hn)
+        h = torch.where((lens > t).unsqueeze(1), (1.0 - z) * n + z * h, h)
+    return h
 
 
 def fm2(v: torch.Tensor) -> torch.Tensor:

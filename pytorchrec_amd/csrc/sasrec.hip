@@ -632,8 +632,18 @@ __global__ __launch_bounds__(256) void sasrec_wgrad_kernel(const float *__restri
                                                            int64_t P, float *__restrict__ grads) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
   if (i >= P) return;
+  // eight loads in flight, added in workgroup order (the same sum, bit for bit, as one
+  // load per addition: that chain of dependent round trips took 61 us over 256 partials)
   float s = 0.f;
-  for (int g = 0; g < parts; ++g) s += part[g * P + i];
+  int g = 0;
+  for (; g + 8 <= parts; g += 8) {
+    float v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = part[(g + k) * P + i];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += v[k];
+  }
+  for (; g < parts; ++g) s += part[g * P + i];
   grads[i] = s;
 }
 

@@ -1063,6 +1063,117 @@ def sasrec_encode(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor,
                                   rnd=cpu_path.bf16_round if rows.is_cuda else None)
 
 
+# the fused GRU4Rec encoder (mrec_gru_*, gru.hip) is the default for the compiled shapes;
+# False selects the layered path (the parity tests set it)
+GRU_FUSED = True
+
+
+def gru_supported(E: int, H: int, L: int) -> bool:
+    """True when the fused recurrence covers (E, H, L).  Decided from the shape alone;
+    never an error."""
+    return bool(_mrec.lib().mrec_gru_supported(int(E), int(H), int(L)))
+
+
+def _gru_params(model):
+    rnn = model.rnn
+    return (rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0)
+
+
+class _GruFn(torch.autograd.Function):
+    """The whole GRU recurrence over the gathered history rows [B, L, E]: one forward
+    launch (-> h_last [B, H], the fp32 hidden sequence saved), one backward launch (the
+    rows' bf16 gradient + per-workgroup partials of the four dense gradients) and the
+    partials' fixed-order sum (mrec_sasrec_wgrad, which is shape-agnostic)."""
+
+    @staticmethod
+    def forward(ctx, rows, his_len, order, check: bool, w_ih, w_hh, b_ih, b_hh):
+        B, L, E = rows.shape
+        H = w_hh.shape[1]
+        dev = rows.device
+        rows2 = _bf16_rows(rows.reshape(B * L, E))
+        his_len = his_len.reshape(-1).to(torch.int32).contiguous()
+        if order is not None:
+            order = order.reshape(-1).to(torch.int32).contiguous()
+        ws = [_weight_f32(w_ih), _weight_f32(w_hh), _f32c(b_ih), _f32c(b_hh)]
+        hs = torch.empty(B, L, H, dtype=torch.float32, device=dev)
+        h_last = torch.empty(B, H, dtype=torch.float32, device=dev)
+        flag = torch.zeros(1, dtype=torch.int32, device=dev) if check else None
+        a = _mrec.GruArgs(
+            rows2.data_ptr(), rows2.stride(0), his_len.data_ptr(), _mrec.ptr(order),
+            ws[0].data_ptr(), ws[0].stride(0), ws[1].data_ptr(), ws[1].stride(0),
+            ws[2].data_ptr(), ws[3].data_ptr(), E, H, L, B, hs.data_ptr(), h_last.data_ptr(),
+            _mrec.ptr(flag), None, None, 0, None, 0)
+        if B:
+            _mrec.call("mrec_gru_fwd", ctypes.byref(a), _mrec.stream_handle())
+        if flag is not None and int(flag.item()) != 0:
+            raise IndexError("index out of range in self")
+        a.d_oob_flag = None
+        ctx.args, ctx.keep = a, (rows2, his_len, order, ws, hs)
+        ctx.params = (w_ih, w_hh, b_ih, b_hh)
+        return h_last
+
+    @staticmethod
+    def backward(ctx, dh):
+        a, (rows2, his_len, order, ws, hs) = ctx.args, ctx.keep
+        params = ctx.params
+        B, L, E, H = int(a.batch), int(a.L), int(a.E), int(a.H)
+        dev = rows2.device
+        dh = dh.detach().float().contiguous()
+        d_rows = torch.empty(B * L, E, dtype=_BF16, device=dev)
+        lib = _mrec.lib()
+        parts = int(lib.mrec_gru_parts(B))
+        P = int(lib.mrec_gru_param_count(E, H))
+        part = torch.empty(parts, P, dtype=torch.float32, device=dev)
+        g = torch.zeros(P, dtype=torch.float32, device=dev)
+        a.dh_last, a.d_rows, a.ld_drows = dh.data_ptr(), d_rows.data_ptr(), d_rows.stride(0)
+        a.part, a.parts = part.data_ptr(), parts
+        st = _mrec.stream_handle()
+        if B:
+            _mrec.call("mrec_gru_bwd", ctypes.byref(a), st)
+            _mrec.call("mrec_sasrec_wgrad", part.data_ptr(), parts, P, g.data_ptr(), st)
+        ctx.args = ctx.keep = None
+        grads = [t.view_as(p) for t, p in
+                 zip(torch.split(g, [3 * H * E, 3 * H * H, 3 * H, 3 * H]), params)]
+        head = (d_rows.reshape(B, L, E), None, None, None)
+        dpg = dp_grads(*params)
+        if dpg is not None:  # data parallel: into the flat buffer IModel all-reduces
+            for dst, src in zip(dpg, grads):
+                dst.copy_(src.view_as(dst))
+            return head + (None,) * 4
+        return head + tuple(grads)
+
+
+def gru_encode(rows: torch.Tensor, his_len: torch.Tensor, model, order="auto") -> torch.Tensor:
+    """h_{his_len - 1} [B, H] (fp32) of ``model.rnn`` (weight_ih_l0, weight_hh_l0,
+    bias_ih_l0, bias_hh_l0) over the gathered history rows [B, L, E].  On a GPU the fused
+    kernels when they cover the shape; else, and on the CPU, the layered path: the same
+    arithmetic as torch ops (``cpu_path.gru_encode``), rounding to bf16 on a GPU where the
+    kernel does.  ``order`` places samples in the kernel's tiles: "sorted" (by length,
+    descending, as the reference's own topk), None (batch order), an int permutation, or
+    "auto": sorted when the batch has more tiles than the launch has workgroups (each
+    workgroup then runs several tiles back to back, and tiles of equal lengths shorten
+    their sum), batch order otherwise (every tile has a workgroup of its own, the launch
+    lasts as long as its longest sample either way, and the sort is pure overhead:
+    DESIGN.md §3.14).  It changes speed only."""
+    from pytorchrec_amd import cpu_path
+    B, L, E = rows.shape
+    params = _gru_params(model)
+    check = bool(getattr(getattr(model, "i_embeddings", None), "check_ids", True))
+    if (rows.is_cuda and GRU_FUSED and gru_supported(E, params[1].shape[1], L)
+            and all(p.dtype == torch.float32 for p in params)):
+        if isinstance(order, str):
+            if order not in ("auto", "sorted"):
+                raise ValueError(f"order must be 'auto', 'sorted', None or a permutation: {order}")
+            lib = _mrec.lib()
+            if order == "sorted" or B > int(lib.mrec_gru_parts(B)) * int(lib.mrec_gru_tile()):
+                order = torch.argsort(his_len.reshape(-1), descending=True, stable=True)
+            else:
+                order = None
+        return _GruFn.apply(rows, his_len, order, check, *params)
+    return cpu_path.gru_encode(rows, his_len, *params,
+                               rnd=cpu_path.bf16_round if rows.is_cuda else None, check=check)
+
+
 def colsum(s: torch.Tensor, X: Optional[torch.Tensor], want_total: bool = True, *,
            out: Optional[torch.Tensor] = None, total: Optional[torch.Tensor] = None,
            sgd_lr: Optional[float] = None):

@@ -76,6 +76,17 @@ def _load_pre_hook(module, state_dict, prefix, local_metadata, strict, missing_k
     state_dict[prefix + _I_KEY] = w
 
 
+def draw_items(bank, emb_size: int, std: float):
+    """normal(0, std) for a single-table item bank, drawn on the CPU default generator in
+    the reference's shape like its CPU-built model, then copied."""
+    t = torch.empty(bank.total_rows, emb_size)
+    torch.nn.init.normal_(t, mean=0.0, std=std)
+    with torch.no_grad():
+        if bank.row_stride != emb_size:
+            bank.weight.zero_()  # row padding stays zero
+        bank.table(0).copy_(t.to(bank.weight.dtype))
+
+
 class SASRec(IModel):
     # GPU: masked history positions are padding slots of the lookup (see forward);
     # False keeps the plain history ids (A/B, parity tests)
@@ -133,15 +144,7 @@ class SASRec(IModel):
         self.layer_norm = LayerNorm(D)
 
     def _draw_items(self, std: float):
-        """normal(0, std) for the item table, drawn on the CPU default generator in the
-        reference's shape like its CPU-built model, then copied."""
-        bank = self.i_embeddings
-        t = torch.empty(bank.total_rows, self.emb_size)
-        torch.nn.init.normal_(t, mean=0.0, std=std)
-        with torch.no_grad():
-            if bank.row_stride != self.emb_size:
-                bank.weight.zero_()  # row padding stays zero
-            bank.table(0).copy_(t.to(bank.weight.dtype))
+        draw_items(self.i_embeddings, self.emb_size, std)
 
     def _reset_weights(self):
         # IModel._reset_weights_fn in registration order (IModel.py:61-68): the two

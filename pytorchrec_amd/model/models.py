@@ -5,6 +5,7 @@ from pytorchrec_amd.model.DCNv2 import DCNv2
 from pytorchrec_amd.model.DeepFM import FM, DeepFM
 from pytorchrec_amd.model.DIN import DIN
 from pytorchrec_amd.model.FunkSVD import FunkSVD
+from pytorchrec_amd.model.GRU4Rec import GRU4Rec
 from pytorchrec_amd.model.IModel import IModel
 from pytorchrec_amd.model.SASRec import SASRec
 from pytorchrec_amd.model.SVDPP import SVDPP
@@ -13,6 +14,7 @@ _model_classes: Dict[str, Type[IModel]] = {
     "funksvd": FunkSVD,
     "svdpp": SVDPP,
     "sasrec": SASRec,
+    "gru4rec": GRU4Rec,
     "fm": FM,
     "deepfm": DeepFM,
     "dcnv2": DCNv2,
