@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MREC_ABI_VERSION 33
+#define MREC_ABI_VERSION 34
 #define MREC_MAX_TABLES 64      /* tables per table bank / per call */
 #define MREC_BWD_MAX_BATCH 8192  /* lookups per table per plan/apply call */
 #define MREC_BWD_HASH_MAX_BATCH 4096  /* batches up to this use the hash plan */
@@ -1564,6 +1564,69 @@ int64_t mrec_gru_parts(int64_t batch);
 int64_t mrec_gru_param_count(int32_t E, int32_t H);
 mrec_status mrec_gru_fwd(const mrec_gru_args *args, mrec_stream stream);
 mrec_status mrec_gru_bwd(const mrec_gru_args *args, mrec_stream stream);
+
+/* ------------------------------------------------------------------------- */
+/* NCF / NeuMF pair scorer, the whole scorer per launch (ABI 34; csrc/ncf.hip)  */
+/* ------------------------------------------------------------------------- */
+/*
+ * The scorer of torchrec/model/NCF.py:62-74 in one launch each way.  Per pair p:
+ *   rows[p] = [mf_u | mf_i | mlp_u | mlp_i]   (4 E bf16, what one gather over the bank
+ *                                              [users, items, users, items] returns)
+ *   g       = mf_u * mf_i                                                   [E]
+ *   h_0     = [mlp_u | mlp_i],  h_{l+1} = relu(w[l] h_l + b[l])   l = 0 .. n_layers - 1
+ *   pred[p] = wp . [g | h_k]
+ * Each weight matrix is rounded to bf16 once, an activation is rounded to bf16 exactly
+ * where it becomes the next layer's operand; every product accumulates in fp32, bias and
+ * ReLU are fp32, g and the final dot are fp32 from the bf16 rows and the fp32 wp (h_k is
+ * not rounded).  One description for both directions; the forward ignores the
+ * backward's fields and saves nothing: the backward recomputes it with the same MFMAs.
+ *   rows    bf16 [pairs] rows, row stride ld_rows elements (16-byte aligned rows:
+ *           ld_rows a multiple of 8, >= 4 E);
+ *   widths  the n_layers hidden widths; w[l] [widths[l], widths[l-1]] (widths[-1] = 2 E,
+ *           row stride ld_w[l]), b[l] [widths[l]], wp [E + widths[n_layers-1]]: the fp32
+ *           masters in nn.Linear layout;
+ *   pred    [pairs] fp32 (forward);
+ *   dpred   [pairs] fp32; d_rows (row stride ld_drows, a multiple of 8, >= 4 E) the rows'
+ *           bf16 gradient in the rows' layout, one rounding from fp32; columns >= 4 E and
+ *           rows >= pairs are not written; part [parts][mrec_ncf_param_count] fp32
+ *           per-workgroup partials of the dense gradients, flat
+ *           [dw[0] | .. | dw[k-1] | db[0] | .. | db[k-1] | dwp], each dw[l] dense
+ *           [widths[l], widths[l-1]] (parts = mrec_ncf_parts(pairs)), to be summed in
+ *           workgroup order by mrec_sasrec_wgrad.  No atomics: two runs give equal bits,
+ *           and a pair's bits do not depend on its place in the batch.
+ * Compiled shapes (mrec_ncf_supported, decided from the shape alone): E in {8, 16, 32,
+ * 64}, 1 .. 3 layers, widths multiples of 8 in 8 .. 128, as long as the bf16 weight
+ * images and the tile buffers fit a CU's 160 KB of LDS and the weight gradients fit the
+ * accumulator registers (at most 128 tiles of 16 x 16): every tower that narrows from
+ * 128, such as (64, [128, 64, 32]), and (64, [128, 128]) fit; (64, [128, 128, 128]) does
+ * not.  A workgroup takes mrec_ncf_tile() pairs at a time.  Stream-ordered, no
+ * allocation, no pointer kept; anything else is MREC_EINVAL before any device work.
+ */
+typedef struct {
+  const void *rows;
+  int64_t ld_rows;
+  int64_t pairs;
+  int32_t E;
+  int32_t n_layers;
+  int32_t widths[3];
+  const float *w[3];
+  int64_t ld_w[3];
+  const float *b[3];
+  const float *wp;
+  float *pred;
+  const float *dpred;
+  void *d_rows;
+  int64_t ld_drows;
+  float *part;
+  int64_t parts;
+} mrec_ncf_args;
+
+int32_t mrec_ncf_supported(int32_t E, int32_t n_layers, const int32_t *widths);
+int32_t mrec_ncf_tile(void);
+int64_t mrec_ncf_parts(int64_t pairs);
+int64_t mrec_ncf_param_count(int32_t E, int32_t n_layers, const int32_t *widths);
+mrec_status mrec_ncf_fwd(const mrec_ncf_args *args, mrec_stream stream);
+mrec_status mrec_ncf_bwd(const mrec_ncf_args *args, mrec_stream stream);
 
 #ifdef __cplusplus
 }

@@ -20,7 +20,7 @@ import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("MREC_LIB_PATH") or os.path.join(LIB_DIR, "libmrec.so")
 
-ABI_VERSION = 33
+ABI_VERSION = 34
 MAX_TABLES = 64
 BWD_MAX_BATCH = 8192
 BWD_HASH_MAX_BATCH = 4096  # batches up to this use the hash plan (fusable into a GEMM launch)
@@ -245,6 +245,18 @@ class GruArgs(ctypes.Structure):
                 ("part", ctypes.c_void_p), ("parts", ctypes.c_int64)]
 
 
+class NcfArgs(ctypes.Structure):
+    """mrec_ncf_args (include/mrec.h, ABI 34): one description for both directions."""
+    _fields_ = [("rows", ctypes.c_void_p), ("ld_rows", ctypes.c_int64), ("pairs", ctypes.c_int64),
+                ("E", ctypes.c_int32), ("n_layers", ctypes.c_int32),
+                ("widths", ctypes.c_int32 * 3),
+                ("w", ctypes.c_void_p * 3), ("ld_w", ctypes.c_int64 * 3),
+                ("b", ctypes.c_void_p * 3), ("wp", ctypes.c_void_p),
+                ("pred", ctypes.c_void_p), ("dpred", ctypes.c_void_p),
+                ("d_rows", ctypes.c_void_p), ("ld_drows", ctypes.c_int64),
+                ("part", ctypes.c_void_p), ("parts", ctypes.c_int64)]
+
+
 LAYOUT_ROW, LAYOUT_COL = 0, 1
 ACT_NONE, ACT_RELU = 0, 1
 
@@ -430,6 +442,12 @@ SIGNATURES = {
     "mrec_gru_param_count": (ctypes.c_int64, [_i32, _i32]),
     "mrec_gru_fwd": (ctypes.c_int, [ctypes.POINTER(GruArgs), _vp]),
     "mrec_gru_bwd": (ctypes.c_int, [ctypes.POINTER(GruArgs), _vp]),
+    "mrec_ncf_supported": (ctypes.c_int32, [_i32, _i32, ctypes.POINTER(_i32)]),
+    "mrec_ncf_tile": (ctypes.c_int32, []),
+    "mrec_ncf_parts": (ctypes.c_int64, [_i64]),
+    "mrec_ncf_param_count": (ctypes.c_int64, [_i32, _i32, ctypes.POINTER(_i32)]),
+    "mrec_ncf_fwd": (ctypes.c_int, [ctypes.POINTER(NcfArgs), _vp]),
+    "mrec_ncf_bwd": (ctypes.c_int, [ctypes.POINTER(NcfArgs), _vp]),
     "mrec_tower_fwd_bwd": (ctypes.c_int, [ctypes.POINTER(TowerArgs), _vp]),
     "mrec_tower_image_elems": (ctypes.c_int64, [_i64, _i64, _i32]),
     "mrec_tower_weight_prep": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),

@@ -226,6 +226,32 @@ def gru_encode(rows: torch.Tensor, his_len: torch.Tensor, w_ih, w_hh, b_ih, b_hh
     return h
 
 
+def ncf_score(rows: torch.Tensor, E: int, weights, biases, wp, rnd=None, dropout: float = 0.0,
+              training: bool = False) -> torch.Tensor:
+    """The NCF / NeuMF pair scorer (NCF.py:62-74) in fp32 torch ops; autograd is its
+    backward.
+
+    rows [pairs, 4E] = [mf_u | mf_i | mlp_u | mlp_i] (one gather over the bank [users,
+    items, users, items]) -> pred [pairs]:
+        g = mf_u * mf_i;  h_0 = [mlp_u | mlp_i];  h_{l+1} = dropout(relu(W_l h_l + b_l))
+        pred = wp . [g | h_k]
+    ``weights`` / ``biases`` are the hidden layers' nn.Linear parameters, ``wp`` the
+    bias-free prediction weight [1, E + width_k] (or flat).
+
+    ``rnd`` rounds each weight matrix and each MLP operand h_l (identity here;
+    ``bf16_round`` on a GPU, where this is the layered path whose rounding points are the
+    fused kernel's: g, h_k and the final dot stay fp32)."""
+    r = rnd if rnd is not None else (lambda t: t)
+    x = rows.float()
+    g = x[:, :E] * x[:, E:2 * E]
+    h = x[:, 2 * E:4 * E]
+    for w, b in zip(weights, biases):
+        h = torch.relu(r(h) @ r(w.float()).t() + b.float())
+        if training and dropout > 0:
+            h = torch.nn.functional.dropout(h, p=dropout, training=True)
+    return torch.cat([g, h], dim=1) @ wp.float().reshape(-1)
+
+
 def fm2(v: torch.Tensor) -> torch.Tensor:
     s = v.sum(dim=1)
     return 0.5 * (s * s - (v * v).sum(dim=1)).sum(dim=-1)

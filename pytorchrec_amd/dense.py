@@ -1174,6 +1174,107 @@ def gru_encode(rows: torch.Tensor, his_len: torch.Tensor, model, order="auto") -
                                rnd=cpu_path.bf16_round if rows.is_cuda else None, check=check)
 
 
+# the fused NCF pair scorer (mrec_ncf_*, ncf.hip) is the default for the compiled shapes;
+# False selects the layered path (the parity tests and the benchmark set it)
+NCF_FUSED = True
+
+
+def _ncf_widths(widths):
+    ws = [int(w) for w in widths]
+    return len(ws), (ctypes.c_int32 * max(len(ws), 1))(*ws)
+
+
+def ncf_supported(E: int, widths) -> bool:
+    """True when the fused scorer covers (emb_size, hidden widths).  Decided from the
+    shape alone; never an error."""
+    nl, arr = _ncf_widths(widths)
+    return bool(_mrec.lib().mrec_ncf_supported(int(E), nl, arr))
+
+
+def _ncf_params(model):
+    lin = [d.linear for d in model.mlp.mlp]
+    return [m.weight for m in lin], [m.bias for m in lin], model.prediction.weight
+
+
+class _NcfFn(torch.autograd.Function):
+    """The whole NCF scorer over the gathered rows [pairs, 4E]: one forward launch
+    (-> pred [pairs], nothing saved but the rows), one backward launch (the rows' bf16
+    gradient + per-workgroup partials of the dense gradients, the forward recomputed)
+    and the partials' fixed-order sum (mrec_sasrec_wgrad, which is shape-agnostic)."""
+
+    @staticmethod
+    def forward(ctx, rows, E: int, nl: int, *params):
+        # params = w_0 .. w_{k-1}, b_0 .. b_{k-1}, wp
+        pairs = rows.shape[0]
+        dev = rows.device
+        rows2 = _bf16_rows(rows)
+        ws = [_weight_f32(w) for w in params[:nl]]
+        bs = [_f32c(b) for b in params[nl:2 * nl]]
+        wp = _f32c(params[2 * nl]).reshape(-1)
+        pred = torch.empty(pairs, dtype=torch.float32, device=dev)
+        a = _mrec.NcfArgs()
+        a.rows, a.ld_rows, a.pairs = rows2.data_ptr(), rows2.stride(0), pairs
+        a.E, a.n_layers = int(E), int(nl)
+        for l in range(nl):
+            a.widths[l] = ws[l].shape[0]
+            a.w[l], a.ld_w[l], a.b[l] = ws[l].data_ptr(), ws[l].stride(0), bs[l].data_ptr()
+        a.wp, a.pred = wp.data_ptr(), pred.data_ptr()
+        if pairs:
+            _mrec.call("mrec_ncf_fwd", ctypes.byref(a), _mrec.stream_handle())
+        ctx.args, ctx.keep = a, (rows2, ws, bs, wp)
+        ctx.params = params
+        return pred
+
+    @staticmethod
+    def backward(ctx, dpred):
+        a, (rows2, ws, bs, wp) = ctx.args, ctx.keep
+        params = ctx.params
+        pairs, E, nl = int(a.pairs), int(a.E), int(a.n_layers)
+        dev = rows2.device
+        dpred = dpred.detach().float().contiguous()
+        d_rows = torch.empty(pairs, 4 * E, dtype=_BF16, device=dev)
+        lib = _mrec.lib()
+        parts = int(lib.mrec_ncf_parts(pairs))
+        P = int(lib.mrec_ncf_param_count(E, nl, a.widths))
+        part = torch.empty(parts, P, dtype=torch.float32, device=dev)
+        g = torch.zeros(P, dtype=torch.float32, device=dev)
+        a.dpred, a.d_rows, a.ld_drows = dpred.data_ptr(), d_rows.data_ptr(), d_rows.stride(0)
+        a.part, a.parts = part.data_ptr(), parts
+        st = _mrec.stream_handle()
+        if pairs:
+            _mrec.call("mrec_ncf_bwd", ctypes.byref(a), st)
+            _mrec.call("mrec_sasrec_wgrad", part.data_ptr(), parts, P, g.data_ptr(), st)
+        ctx.args = ctx.keep = None
+        sizes = [w.numel() for w in ws] + [b.numel() for b in bs] + [wp.numel()]
+        grads = [t.view_as(p) for t, p in zip(torch.split(g, sizes), params)]
+        head = (d_rows, None, None)
+        dpg = dp_grads(*params)
+        if dpg is not None:  # data parallel: into the flat buffer IModel all-reduces
+            for dst, src in zip(dpg, grads):
+                dst.copy_(src.view_as(dst))
+            return head + (None,) * len(params)
+        return head + tuple(grads)
+
+
+def ncf_score(rows: torch.Tensor, model) -> torch.Tensor:
+    """pred [pairs] (fp32) of ``model``'s NCF scorer (mlp, prediction, emb_size, dropout)
+    over the gathered rows [pairs, 4E] = [mf_u | mf_i | mlp_u | mlp_i].  On a GPU the
+    fused kernels when they cover the shape, the parameters are fp32 and no dropout is
+    active; else, and on the CPU, the layered path: the same arithmetic as torch ops
+    (``cpu_path.ncf_score``), rounding to bf16 on a GPU where the kernel does."""
+    from pytorchrec_amd import cpu_path
+    E = int(model.emb_size)
+    ws, bs, wp = _ncf_params(model)
+    drop = float(model.dropout)
+    if (rows.is_cuda and NCF_FUSED and not (model.training and drop > 0)
+            and ncf_supported(E, [w.shape[0] for w in ws])
+            and all(p.dtype == torch.float32 for p in (*ws, *bs, wp))):
+        return _NcfFn.apply(rows, E, len(ws), *ws, *bs, wp)
+    return cpu_path.ncf_score(rows, E, ws, bs, wp,
+                              rnd=cpu_path.bf16_round if rows.is_cuda else None,
+                              dropout=drop, training=model.training)
+
+
 def colsum(s: torch.Tensor, X: Optional[torch.Tensor], want_total: bool = True, *,
            out: Optional[torch.Tensor] = None, total: Optional[torch.Tensor] = None,
            sgd_lr: Optional[float] = None):

@@ -7,4 +7,5 @@ from pytorchrec_amd.model.FunkSVD import FunkSVD
 from pytorchrec_amd.model.SVDPP import SVDPP
 from pytorchrec_amd.model.SASRec import SASRec
 from pytorchrec_amd.model.GRU4Rec import GRU4Rec
+from pytorchrec_amd.model.NCF import NCF
 from pytorchrec_amd.model.models import get_model_type, model_name_list

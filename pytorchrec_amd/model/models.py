@@ -7,6 +7,7 @@ from pytorchrec_amd.model.DIN import DIN
 from pytorchrec_amd.model.FunkSVD import FunkSVD
 from pytorchrec_amd.model.GRU4Rec import GRU4Rec
 from pytorchrec_amd.model.IModel import IModel
+from pytorchrec_amd.model.NCF import NCF
 from pytorchrec_amd.model.SASRec import SASRec
 from pytorchrec_amd.model.SVDPP import SVDPP
 
@@ -15,6 +16,7 @@ _model_classes: Dict[str, Type[IModel]] = {
     "svdpp": SVDPP,
     "sasrec": SASRec,
     "gru4rec": GRU4Rec,
+    "ncf": NCF,
     "fm": FM,
     "deepfm": DeepFM,
     "dcnv2": DCNv2,
