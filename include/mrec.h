@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MREC_ABI_VERSION 34
+#define MREC_ABI_VERSION 35
 #define MREC_MAX_TABLES 64      /* tables per table bank / per call */
 #define MREC_BWD_MAX_BATCH 8192  /* lookups per table per plan/apply call */
 #define MREC_BWD_HASH_MAX_BATCH 4096  /* batches up to this use the hash plan */
@@ -1627,6 +1627,80 @@ int64_t mrec_ncf_parts(int64_t pairs);
 int64_t mrec_ncf_param_count(int32_t E, int32_t n_layers, const int32_t *widths);
 mrec_status mrec_ncf_fwd(const mrec_ncf_args *args, mrec_stream stream);
 mrec_status mrec_ncf_bwd(const mrec_ncf_args *args, mrec_stream stream);
+
+/* ------------------------------------------------------------------------- */
+/* Retrieval: full-catalogue top-K, score and select fused (ABI 35; csrc/topk.hip) */
+/* ------------------------------------------------------------------------- */
+/*
+ * For queries q [batch, D] (MREC_F32 or MREC_BF16, row stride ldq elements) and table
+ * `table` of `bank` (D = bank->dim), restricted to the table-local item ids [low, high):
+ *   score[b, i] = sum_d bf16(q[b, d]) * bf16(T[i, d])      fp32 accumulation
+ *                 + w[i]                                    fp32, only with use_w (has_w bank)
+ * bf16() is round-to-nearest-even: exact for a bf16 bank, and for an fp32 bank the rounding
+ * a gather of its rows as bf16 applies.  out_ids [batch, k] (int32, table-local) and
+ * out_scores [batch, k] (fp32), common row stride ld_out >= k elements, receive per query
+ * the k best eligible items sorted by the total order SCORE DESCENDING, THEN ID ASCENDING.
+ * Columns >= k and rows >= batch of the outputs are not written.
+ *   Eligibility.  Item i is eligible iff low <= i < high, its score is not NaN and it is
+ *     not excluded.  +0.0 and -0.0 compare equal (the lower id wins; a zero is returned
+ *     as +0.0).  With fewer than k eligible items the remaining slots hold id -1 and score
+ *     -inf; an item whose score is -inf is returned as such a slot.
+ *   Exclusion (optional; all NULL / 0 for none).  A CSR: excl_items[excl_offsets[r] ..
+ *     excl_offsets[r + 1]) (int32, table-local ids, sorted ascending and de-duplicated;
+ *     excl_offsets int64 [excl_n_rows + 1]) are the items excluded for CSR row r -- the
+ *     layout mrec_neg_sample reads.  Query b uses row excl_row[b] (excl_row_dtype MREC_I32
+ *     or MREC_I64), or row b when excl_row is NULL; a row index outside [0, excl_n_rows)
+ *     excludes nothing.  An item is looked up (binary search) only when it would otherwise
+ *     enter the query's kept list, never for every score.
+ *   Determinism.  The total order makes the answer unique, and the result depends on the
+ *     inputs only: never on the launch geometry, on `splits`, on where the bank lies or on
+ *     the order in which candidates arrive.  Two runs, or two split counts, give equal bits.
+ *   Never read: the pad columns of a bank row past [v | w] (w itself only with use_w),
+ *     rows outside [row_offset[table] + low, row_offset[table] + high), columns >= D of q.
+ *     The rows are read as stored: a bank under the lazy fused Adam is flushed first
+ *     (mrec_emb_optim_flush).
+ *   splits: the item range is cut into `splits` parts scanned by different workgroups, 0 =
+ *     mrec_topk_splits(batch, high - low), at most 64.  With more than one split the
+ *     partial lists go through `workspace` (8-byte aligned,
+ *     mrec_topk_workspace_size(batch, k, splits) bytes; splits = 0 there sizes for any
+ *     default) and a second launch merges them.
+ * Compiled shapes (mrec_topk_supported): D in {8, 16, 32, 64}, 1 <= k <= 128, bank F32 or
+ * BF16; batch >= 0 and high - low >= 0 (an empty batch writes nothing, an empty range fills
+ * the padding values).  A workgroup carries mrec_topk_tile_queries() queries and streams
+ * mrec_topk_tile_items() items at a time.  Caller-owned buffers, no allocation, no host
+ * synchronisation, all work on `stream`; anything else is MREC_EINVAL with
+ * mrec_last_error() before any launch.
+ */
+typedef struct {
+  const mrec_table_bank *bank;
+  int32_t table;
+  int64_t low;
+  int64_t high;
+  const void *q;
+  mrec_dtype q_dtype;
+  int64_t ldq;
+  int64_t batch;
+  int32_t k;
+  int32_t use_w;
+  const int64_t *excl_offsets;
+  const int32_t *excl_items;
+  int64_t excl_n_rows;
+  const void *excl_row;
+  mrec_dtype excl_row_dtype;
+  int32_t splits;
+  void *workspace;
+  size_t workspace_bytes;
+  int32_t *out_ids;
+  float *out_scores;
+  int64_t ld_out;
+} mrec_topk_args;
+
+int32_t mrec_topk_supported(int32_t D, int32_t k, mrec_dtype bank_dtype);
+int32_t mrec_topk_tile_queries(void); /* queries a workgroup carries */
+int32_t mrec_topk_tile_items(void);   /* items per streamed tile     */
+int32_t mrec_topk_splits(int64_t batch, int64_t n_items); /* the default item-split count */
+size_t mrec_topk_workspace_size(int64_t batch, int32_t k, int32_t splits);
+mrec_status mrec_topk(const mrec_topk_args *args, mrec_stream stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,8 @@ sampler of ``sampling.NegativeSampler``: the counter hash of ``mrec_neg_sample``
 numpy.  ``sasrec_encode`` is the SASRec encoder in torch ops: the CPU path, and on a GPU
 the layered path for the shapes and modes the fused kernels do not cover
 (``dense.sasrec_encode`` decides); ``gru_encode`` is the same for the GRU4Rec recurrence
-(``dense.gru_encode`` decides).
+(``dense.gru_encode`` decides).  ``topk`` is ``mrec_topk``, the full-catalogue retrieval, in
+torch ops, chunked over the items (``retrieval.topk`` decides).
 """
 from __future__ import annotations
 
@@ -290,3 +291,80 @@ def interact_rows(g: List[torch.Tensor], dim: int, dense: Optional[torch.Tensor]
     if x0.shape[1] < x0_cols:
         x0 = torch.nn.functional.pad(x0, (0, x0_cols - x0.shape[1]))
     return x0.to(x0_dtype), logit
+
+
+def topk_exclusion_pairs(offsets, items, rows, batch: int, device):
+    """The (query, item) pairs of a top-k exclusion, flat: CSR ``offsets`` / ``items``,
+    query b using CSR row ``rows[b]`` (``b`` when None); a row index outside the CSR
+    excludes nothing.  -> (query index int64 [P], item id int64 [P])."""
+    off = offsets.to(device=device, dtype=torch.int64)
+    n_rows = off.numel() - 1
+    r = (torch.arange(batch, device=device) if rows is None
+         else rows.to(device=device, dtype=torch.int64).reshape(-1))
+    ok = (r >= 0) & (r < n_rows)
+    rc = torch.where(ok, r, torch.zeros_like(r))
+    start = off[rc]
+    length = torch.where(ok, off[rc + 1] - start, torch.zeros_like(start))
+    qidx = torch.repeat_interleave(torch.arange(batch, device=device), length)
+    first = torch.cumsum(length, 0) - length
+    pos = torch.arange(qidx.numel(), device=device) - first[qidx] + start[qidx]
+    return qidx, items.to(device)[pos].to(torch.int64)
+
+
+def topk(rows, dim: int, q, k: int, low: int, high: int, use_w: bool, exclude=None,
+         chunk: int = 8192, round_bf16: bool = True):
+    """``mrec_topk`` in torch ops (include/mrec.h "Retrieval"): the k best items of
+    ``[low, high)`` per query by score descending, then id ascending, with the kernel's
+    eligibility, exclusion and padding rules.  ``rows`` is the table ``[items,
+    row_stride]`` (``[v(dim) | w | pad]``, on any device: it is read ``chunk`` rows at a
+    time), ``exclude`` an ``(offsets, items, rows)`` triple or None.  Chunked over the
+    items with a running merge: never more than ``[B, chunk]`` scores exist.
+    ``round_bf16=False`` keeps q and the rows in fp32 (a CPU bank: what the CPU forward
+    of a model computes, which never rounds).
+    -> (ids int32 [B, k], scores float32 [B, k]) on q's device."""
+    dev = q.device
+    B = q.shape[0]
+    def operand(t):
+        return t.to(torch.bfloat16).float() if round_bf16 else t.float()
+
+    qb = operand(q.detach()[:, :dim])
+    neg_inf = float("-inf")
+    best_s = torch.full((B, k), neg_inf, dtype=torch.float32, device=dev)
+    best_i = torch.full((B, k), -1, dtype=torch.int64, device=dev)
+    pairs = None
+    if exclude is not None and B > 0:
+        pairs = topk_exclusion_pairs(exclude[0], exclude[1], exclude[2], B, dev)
+    chunk = max(1, int(chunk))
+    for c0 in range(low, high, chunk):
+        c1 = min(high, c0 + chunk)
+        blk = rows[c0:c1].detach().to(dev)
+        s = qb @ operand(blk[:, :dim]).t()
+        if use_w:
+            s = s + blk[:, dim].float().unsqueeze(0)
+        best_s, best_i = topk_fold(best_s, best_i, s, c0, pairs)
+    return topk_finish(best_s, best_i)
+
+
+def topk_fold(best_s, best_i, s, c0: int, pairs=None):
+    """Fold the scores ``s [B, n]`` of items ``c0 .. c0 + n - 1`` into the running lists
+    ``(best_s, best_i) [B, k]`` of a scan in ascending id order.  NaN scores and the
+    excluded ``pairs`` (``topk_exclusion_pairs``) drop to -inf."""
+    B, n = s.shape
+    k = best_s.shape[1]
+    neg_inf = float("-inf")
+    s = torch.where(torch.isnan(s), torch.full_like(s, neg_inf), s) + 0.0  # (-0.0 -> +0.0)
+    if pairs is not None:
+        qidx, it = pairs
+        m = (it >= c0) & (it < c0 + n)
+        s[qidx[m], it[m] - c0] = neg_inf
+    ids = torch.arange(c0, c0 + n, device=s.device).unsqueeze(0).expand(B, n)
+    # kept ids are below the chunk's and ties within each part are in id order: a
+    # stable descending sort of [kept | chunk] is the total order
+    cs, order = torch.sort(torch.cat([best_s, s], 1), dim=1, descending=True, stable=True)
+    return cs[:, :k].contiguous(), torch.gather(torch.cat([best_i, ids], 1), 1, order[:, :k])
+
+
+def topk_finish(best_s, best_i):
+    """-> (ids int32, scores float32): a slot whose score is -inf is padding, id -1."""
+    best_i = torch.where(best_s == float("-inf"), torch.full_like(best_i, -1), best_i)
+    return best_i.to(torch.int32), best_s

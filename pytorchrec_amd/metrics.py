@@ -93,6 +93,26 @@ def rank_pos_device(prediction):
     return out
 
 
+def topk_pos_rank(ids, pos):
+    """The 1-based place of ``pos[b]`` in the retrieved list ``ids[b]`` (``[B, K]``), or
+    ``K + 1`` when it is absent: the positive's rank among ALL items wherever it is at most
+    K, so ``NDCG(., k).fast_calc`` / ``Hit(., k).fast_calc`` of it are the full-catalogue
+    NDCG@k / Hit@k for k <= K.  Torch tensors give an int64 tensor on their device, anything
+    else an int64 numpy array."""
+    import torch
+    as_numpy = not torch.is_tensor(ids)
+    t = torch.as_tensor(np.asarray(ids)) if as_numpy else ids
+    p = torch.as_tensor(np.asarray(pos)) if not torch.is_tensor(pos) else pos
+    if t.dim() != 2 or p.reshape(-1).shape[0] != t.shape[0]:
+        raise ValueError("topk_pos_rank needs ids [B, K] and pos [B]")
+    K = t.shape[1]
+    hit = t.to(torch.int64) == p.reshape(-1, 1).to(device=t.device, dtype=torch.int64)
+    place = torch.arange(1, K + 1, device=t.device).unsqueeze(0).expand_as(hit)
+    rank = torch.where(hit, place, torch.full_like(place, K + 1)).amin(dim=1) if K else \
+        torch.ones(t.shape[0], dtype=torch.int64, device=t.device)
+    return rank.numpy() if as_numpy else rank
+
+
 class RankingMetric:
     """Base of the leave-one-out metrics (torchrec/metric/IMetric.py): a metric of the
     positives' ranks alone, so ``IModel.evaluate`` may feed it ranks computed on the

@@ -115,6 +115,42 @@ class GRU4Rec(IModel):
             self.rnn.to(self.build_device)
             self.out.to(self.build_device)
 
+    candidate_lists = True
+
+    def _history_lookup_ids(self, his: Tensor, his_len: Tensor):
+        """The history's lookup ids, flat ``[B L]``, and whether negative ones are padding
+        slots of the gather."""
+        bank = self.i_embeddings
+        live = torch.arange(his.shape[1], device=his.device).unsqueeze(0) < his_len.reshape(-1, 1)
+        if bank.weight.is_cuda and self.pad_skip:
+            # positions past the length (never read by the recurrence: an exactly zero
+            # gradient) become padding slots (-1): zero rows forward, skipped by the
+            # backward.  A negative id anywhere else stays out of range (IndexError).
+            past = torch.full_like(his, bank.category_nums[0])
+            return torch.where(live, torch.where(his < 0, past, his),
+                               torch.full_like(his, -1)).reshape(-1), True
+        # the ids past the length never matter: row 0 stands in for them
+        return torch.where(live, his, torch.zeros_like(his)).reshape(-1), False
+
+    def _session_vector(self, rows: Tensor, his_len: Tensor) -> Tensor:
+        """v = out(h_last) [B, E] fp32 from the history rows [B, L, E]."""
+        h = dense_ops.gru_encode(rows, his_len, self, order=self.tile_order)
+        return dense_ops.linear(h, self.out.weight, None, out_dtype=torch.float32)
+
+    def _retrieval_query(self, data: Dict[str, Tensor]):
+        """``recommend``: the score is v . i with v = out(h), from a history-only lookup."""
+        his = self.his_column.get_feature_ids(data)
+        his_len = self.his_len_column.get_feature_ids(data)
+        if his.dim() != 2:
+            raise ValueError(f"his must be [B, L], got {tuple(his.shape)}")
+        B, L = his.shape
+        bank = self.i_embeddings
+        act_dtype = torch.bfloat16 if bank.weight.is_cuda else torch.float32
+        hist_ids, padded = self._history_lookup_ids(his, his_len)
+        rows = gather(bank, [hist_ids], out_dtype=act_dtype, pad_negative=padded)
+        v = self._session_vector(rows.reshape(B, L, self.emb_size), his_len)
+        return v.float(), bank, 0, False, None
+
     def forward(self, data: Dict[str, Tensor]):
         i_ids = self.iid_column.get_feature_ids(data)
         his = self.his_column.get_feature_ids(data)
@@ -129,27 +165,15 @@ class GRU4Rec(IModel):
         bank = self.i_embeddings
         on_gpu = bank.weight.is_cuda
         act_dtype = torch.bfloat16 if on_gpu else torch.float32
-        live = torch.arange(L, device=his.device).unsqueeze(0) < his_len.reshape(-1, 1)
         # history and candidate rows in ONE lookup (one sorted-segment backward, one
         # update per row, as a single nn.Embedding would do)
-        if on_gpu and self.pad_skip:
-            # positions past the length (never read by the recurrence: an exactly zero
-            # gradient) become padding slots (-1): zero rows forward, skipped by the
-            # backward.  A negative id anywhere else stays out of range (IndexError).
-            past = torch.full_like(his, bank.category_nums[0])
-            cand = i_ids.reshape(-1).to(his.dtype)
-            ids = torch.cat([torch.where(live, torch.where(his < 0, past, his),
-                                         torch.full_like(his, -1)).reshape(-1),
-                             torch.where(cand < 0, past.reshape(-1)[:1], cand)])
-            rows = gather(bank, [ids], out_dtype=act_dtype, pad_negative=True)
-        else:
-            # the ids past the length never matter: row 0 stands in for them
-            ids = torch.cat([torch.where(live, his, torch.zeros_like(his)).reshape(-1),
-                             i_ids.reshape(-1).to(his.dtype)])
-            rows = gather(bank, [ids], out_dtype=act_dtype)
-        h = dense_ops.gru_encode(rows[:B * L].reshape(B, L, E), his_len, self,
-                                 order=self.tile_order)
-        v = dense_ops.linear(h, self.out.weight, None, out_dtype=torch.float32)
+        hist_ids, padded = self._history_lookup_ids(his, his_len)
+        cand = i_ids.reshape(-1).to(his.dtype)
+        if padded:
+            past = torch.full_like(his.reshape(-1)[:1], bank.category_nums[0])
+            cand = torch.where(cand < 0, past, cand)
+        rows = gather(bank, [torch.cat([hist_ids, cand])], out_dtype=act_dtype, pad_negative=padded)
+        v = self._session_vector(rows[:B * L].reshape(B, L, E), his_len)
         prediction = (v.float().unsqueeze(1) * rows[B * L:].reshape(B, N, E).float()).sum(-1)
         target = None
         if self.label_column is not None and self.label_column.feature_name in data:

@@ -32,6 +32,10 @@ Checkpoint compatibility: ``state_dict`` / ``load_state_dict`` speak the referen
 (the four Embedding constructors, the MLP's Linears, ``prediction``; then
 ``IModel._reset_weights_fn`` in registration order), so the same ``random_seed`` gives
 bit-identical parameters (golden G17).
+
+``recommend`` (full-catalogue top-k) runs the generic path of ``IModel``: the item range
+goes through ``forward`` in chunks of candidates.  The scorer is an MLP over the pair,
+not a dot product with an item row, so the fused retrieval kernel does not apply.
 """
 from typing import Any, Dict, List
 
@@ -157,6 +161,8 @@ class NCF(IModel):
         if self.build_device is not None:
             self.mlp.to(self.build_device)
             self.prediction.to(self.build_device)
+
+    candidate_lists = True  # (recommend: IModel's generic path, see the module docstring)
 
     def forward(self, data: Dict[str, Tensor]):
         u_ids = self.uid_column.get_feature_ids(data)

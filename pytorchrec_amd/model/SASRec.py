@@ -157,6 +157,41 @@ class SASRec(IModel):
             for m in (self.p_embeddings, self.Q, self.K, self.W1, self.W2, self.layer_norm):
                 m.to(self.build_device)
 
+    candidate_lists = True
+    retrieval_low = 1  # id 0 is the padding item
+
+    def _history_lookup_ids(self, his: Tensor):
+        """The history's lookup ids, flat ``[B L]``, and whether negative ones are padding
+        slots of the gather."""
+        bank = self.i_embeddings
+        if not (bank.weight.is_cuda and self.pad_skip):
+            return his.reshape(-1), False
+        # masked history positions (never a key, dropped from v: an exactly zero
+        # gradient) become padding slots (-1): zero rows forward, skipped by the
+        # backward, so the PAD row is not a ~B L / 2-lookup hot row of every step's
+        # update.  A negative id anywhere else stays out of range (IndexError).
+        past = torch.full_like(his, bank.category_nums[0])
+        pad = torch.where(his < 0, past, torch.full_like(his, -1))
+        pad[:, 0] += his[:, 0] == 0  # position 0 is forced valid: the PAD row itself
+        return torch.where(his > 0, his, pad).reshape(-1), True
+
+    def _encode_history(self, data: Dict[str, Tensor]) -> Tensor:
+        """v [B, D] from a history-only lookup (``recommend``: no candidates to gather)."""
+        his = self.his_column.get_feature_ids(data)
+        his_len = self.his_len_column.get_feature_ids(data)
+        if his.dim() != 2:
+            raise ValueError(f"his must be [B, L], got {tuple(his.shape)}")
+        B, L = his.shape
+        bank = self.i_embeddings
+        act_dtype = torch.bfloat16 if bank.weight.is_cuda else torch.float32
+        hist_ids, padded = self._history_lookup_ids(his)
+        rows = gather(bank, [hist_ids], out_dtype=act_dtype, pad_negative=padded)
+        return dense_ops.sasrec_encode(rows.reshape(B, L, self.emb_size), his, his_len, self)
+
+    def _retrieval_query(self, data: Dict[str, Tensor]):
+        """``recommend``: the score is v . i, the query the encoder's output."""
+        return self._encode_history(data).float(), self.i_embeddings, 0, False, None
+
     def forward(self, data: Dict[str, Tensor]):
         i_ids = self.iid_column.get_feature_ids(data)
         his = self.his_column.get_feature_ids(data)
@@ -172,21 +207,12 @@ class SASRec(IModel):
         act_dtype = torch.bfloat16 if bank.weight.is_cuda else torch.float32
         # history and candidate rows in ONE lookup (one sorted-segment backward, one
         # update per row, as a single nn.Embedding would do)
-        if bank.weight.is_cuda and self.pad_skip:
-            # masked history positions (never a key, dropped from v: an exactly zero
-            # gradient) become padding slots (-1): zero rows forward, skipped by the
-            # backward, so the PAD row is not a ~B L / 2-lookup hot row of every step's
-            # update.  A negative id anywhere else stays out of range (IndexError).
-            past = torch.full_like(his, bank.category_nums[0])
-            pad = torch.where(his < 0, past, torch.full_like(his, -1))
-            pad[:, 0] += his[:, 0] == 0  # position 0 is forced valid: the PAD row itself
-            cand = i_ids.reshape(-1).to(his.dtype)
-            ids = torch.cat([torch.where(his > 0, his, pad).reshape(-1),
-                             torch.where(cand < 0, past.reshape(-1)[:1], cand)])
-            rows = gather(bank, [ids], out_dtype=act_dtype, pad_negative=True)
-        else:
-            ids = torch.cat([his.reshape(-1), i_ids.reshape(-1).to(his.dtype)])
-            rows = gather(bank, [ids], out_dtype=act_dtype)
+        hist_ids, padded = self._history_lookup_ids(his)
+        cand = i_ids.reshape(-1).to(his.dtype)
+        if padded:
+            past = torch.full_like(his.reshape(-1)[:1], bank.category_nums[0])
+            cand = torch.where(cand < 0, past, cand)
+        rows = gather(bank, [torch.cat([hist_ids, cand])], out_dtype=act_dtype, pad_negative=padded)
         v = dense_ops.sasrec_encode(rows[:B * L].reshape(B, L, D), his, his_len, self)
         prediction = (v.unsqueeze(1) * rows[B * L:].reshape(B, N, D).float()).sum(-1)
         target = None
