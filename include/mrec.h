@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MREC_ABI_VERSION 35
+#define MREC_ABI_VERSION 36
 #define MREC_MAX_TABLES 64      /* tables per table bank / per call */
 #define MREC_BWD_MAX_BATCH 8192  /* lookups per table per plan/apply call */
 #define MREC_BWD_HASH_MAX_BATCH 4096  /* batches up to this use the hash plan */
@@ -1701,6 +1701,94 @@ int32_t mrec_topk_tile_items(void);   /* items per streamed tile     */
 int32_t mrec_topk_splits(int64_t batch, int64_t n_items); /* the default item-split count */
 size_t mrec_topk_workspace_size(int64_t batch, int32_t k, int32_t splits);
 mrec_status mrec_topk(const mrec_topk_args *args, mrec_stream stream);
+
+/* ------------------------------------------------------------------------- */
+/* NCF retrieval: full-catalogue top-K with the NeuMF scorer (ABI 36; csrc/ncf_topk.hip) */
+/* ------------------------------------------------------------------------- */
+/*
+ * For the users uid [batch] (MREC_I32 or MREC_I64) and every item i of the table-local
+ * range [low, high), the score of mrec_ncf_fwd for the pair (u = uid[b], i) -- without the
+ * gathered row and without the [batch, items] scores ever reaching memory -- fused with
+ * the selection of mrec_topk.  The four tables are tables of one bank (E = bank->dim):
+ * table_mf_u and table_mlp_u have one row per user, table_mf_i and table_mlp_i one per
+ * item.  The score contract: every table element is used as its bf16 value (round to
+ * nearest even from an fp32 bank: what a gather of the row as bf16 gives), every w[l] is
+ * rounded to bf16 once per workgroup, and
+ *   a[b, n]   = b[0][n] + sum_e w[0][n, e]     * mlp_u[u, e]      fp32, once per user
+ *   c[i, n]   =           sum_e w[0][n, E + e] * mlp_i[i, e]      fp32, once per item (tile)
+ *   h_1       = relu(a[b] + c[i])
+ *   h_{l+1}   = relu(w[l] h_l + b[l])     l = 1 .. n_layers - 1, as mrec_ncf_fwd computes it
+ *   score     = sum_e wp[e] * (mf_u[u, e] * mf_i[i, e])  +  wp[E:] . h_{n_layers}
+ * relu(x) is mrec_ncf_fwd's `x > 0 ? x : 0`: a NaN pre-activation gives 0, so a NaN in an mlp
+ * row does not reach the score; a NaN in an mf row does, and that item is not eligible.
+ * The rounding points are mrec_ncf_fwd's: each h_l is rounded to bf16 where it becomes the
+ * next layer's operand; the last layer's output, g = mf_u * mf_i and the final dot stay
+ * fp32 (with one layer h_1 is the last and is not rounded).  Against mrec_ncf_fwd only the
+ * fp32 summation order of layer 0 differs (its user half and its item half are summed
+ * separately).  A pair's score bits depend on the pair alone: not on its tile, its place
+ * in the batch, the split count or where the bank lies.
+ *   Selection.  Eligibility, exclusion (excl_* as in mrec_topk_args, row b of the CSR or
+ *     row excl_row[b]), the total order SCORE DESCENDING, THEN ID ASCENDING, the padding
+ *     (id -1, score -inf), `splits` and the workspace are those of mrec_topk, word for
+ *     word; a NaN score is never returned; two runs, or two split counts, give equal bits.
+ *   User ids.  A uid outside [0, rows of the user tables) is never used as a table index:
+ *     it sets *d_oob_flag to 1 (when non-NULL) and its output row is all padding.
+ *   Never read: the pad columns of a bank row past the embedding, item rows outside
+ *     [low, high), user rows no uid names.  The rows are read as stored: a bank under the
+ *     lazy fused Adam is flushed first (mrec_emb_optim_flush).
+ * widths, w, ld_w, b, wp: the fp32 masters in nn.Linear layout, as in mrec_ncf_args (w[0]
+ * is [widths[0], 2 E]).  Compiled shapes (mrec_ncf_topk_supported, decided from the shape
+ * alone): those of mrec_ncf_supported -- E in {8, 16, 32, 64}, 1 .. 3 layers, widths
+ * multiples of 8 in 8 .. 128 -- with 1 <= k <= 128 and an F32 or BF16 bank, as long as the
+ * weight images, the tile buffers and the per-user key buffers (which grow with k) fit a
+ * CU's 160 KB of LDS: (64, [128, 64, 32]) fits at k = 128.  A workgroup carries
+ * mrec_ncf_topk_tile_users() users and streams mrec_ncf_topk_tile_items() items at a time;
+ * mrec_ncf_topk_splits(batch, high - low) is the default split count, and
+ * mrec_ncf_topk_workspace_size(batch, k, splits) sizes the workspace (8-byte aligned;
+ * splits = 0 sizes for any default).  batch >= 0 and high - low >= 0 (an empty batch writes
+ * nothing, an empty range fills the padding values).  Caller-owned buffers, no allocation,
+ * no host synchronisation, all work on `stream`; anything else is MREC_EINVAL with
+ * mrec_last_error() before any launch.
+ */
+typedef struct {
+  const mrec_table_bank *bank;
+  int32_t table_mf_u;
+  int32_t table_mf_i;
+  int32_t table_mlp_u;
+  int32_t table_mlp_i;
+  int64_t low;
+  int64_t high;
+  const void *uid;
+  mrec_dtype uid_dtype;
+  int64_t batch;
+  int32_t n_layers;
+  int32_t widths[3];
+  const float *w[3];
+  int64_t ld_w[3];
+  const float *b[3];
+  const float *wp;
+  int32_t k;
+  int32_t splits;
+  const int64_t *excl_offsets;
+  const int32_t *excl_items;
+  int64_t excl_n_rows;
+  const void *excl_row;
+  mrec_dtype excl_row_dtype;
+  int32_t *d_oob_flag;
+  void *workspace;
+  size_t workspace_bytes;
+  int32_t *out_ids;
+  float *out_scores;
+  int64_t ld_out;
+} mrec_ncf_topk_args;
+
+int32_t mrec_ncf_topk_supported(int32_t E, int32_t n_layers, const int32_t *widths, int32_t k,
+                                mrec_dtype bank_dtype);
+int32_t mrec_ncf_topk_tile_users(void); /* users a workgroup carries */
+int32_t mrec_ncf_topk_tile_items(void); /* items per streamed tile   */
+int32_t mrec_ncf_topk_splits(int64_t batch, int64_t n_items); /* the default item-split count */
+size_t mrec_ncf_topk_workspace_size(int64_t batch, int32_t k, int32_t splits);
+mrec_status mrec_ncf_topk(const mrec_ncf_topk_args *args, mrec_stream stream);
 
 #ifdef __cplusplus
 }

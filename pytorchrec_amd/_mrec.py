@@ -20,7 +20,7 @@ import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("MREC_LIB_PATH") or os.path.join(LIB_DIR, "libmrec.so")
 
-ABI_VERSION = 35
+ABI_VERSION = 36
 MAX_TABLES = 64
 BWD_MAX_BATCH = 8192
 BWD_HASH_MAX_BATCH = 4096  # batches up to this use the hash plan (fusable into a GEMM launch)
@@ -271,6 +271,25 @@ class TopkArgs(ctypes.Structure):
                 ("ld_out", ctypes.c_int64)]
 
 
+class NcfTopkArgs(ctypes.Structure):
+    """mrec_ncf_topk_args (include/mrec.h, ABI 36)."""
+    _fields_ = [("bank", ctypes.POINTER(TableBank)),
+                ("table_mf_u", ctypes.c_int32), ("table_mf_i", ctypes.c_int32),
+                ("table_mlp_u", ctypes.c_int32), ("table_mlp_i", ctypes.c_int32),
+                ("low", ctypes.c_int64), ("high", ctypes.c_int64),
+                ("uid", ctypes.c_void_p), ("uid_dtype", ctypes.c_int), ("batch", ctypes.c_int64),
+                ("n_layers", ctypes.c_int32), ("widths", ctypes.c_int32 * 3),
+                ("w", ctypes.c_void_p * 3), ("ld_w", ctypes.c_int64 * 3),
+                ("b", ctypes.c_void_p * 3), ("wp", ctypes.c_void_p),
+                ("k", ctypes.c_int32), ("splits", ctypes.c_int32),
+                ("excl_offsets", ctypes.c_void_p), ("excl_items", ctypes.c_void_p),
+                ("excl_n_rows", ctypes.c_int64), ("excl_row", ctypes.c_void_p),
+                ("excl_row_dtype", ctypes.c_int), ("d_oob_flag", ctypes.c_void_p),
+                ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+                ("out_ids", ctypes.c_void_p), ("out_scores", ctypes.c_void_p),
+                ("ld_out", ctypes.c_int64)]
+
+
 LAYOUT_ROW, LAYOUT_COL = 0, 1
 ACT_NONE, ACT_RELU = 0, 1
 
@@ -468,6 +487,12 @@ SIGNATURES = {
     "mrec_topk_splits": (ctypes.c_int32, [_i64, _i64]),
     "mrec_topk_workspace_size": (ctypes.c_size_t, [_i64, _i32, _i32]),
     "mrec_topk": (ctypes.c_int, [ctypes.POINTER(TopkArgs), _vp]),
+    "mrec_ncf_topk_supported": (ctypes.c_int32, [_i32, _i32, ctypes.POINTER(_i32), _i32, ctypes.c_int]),
+    "mrec_ncf_topk_tile_users": (ctypes.c_int32, []),
+    "mrec_ncf_topk_tile_items": (ctypes.c_int32, []),
+    "mrec_ncf_topk_splits": (ctypes.c_int32, [_i64, _i64]),
+    "mrec_ncf_topk_workspace_size": (ctypes.c_size_t, [_i64, _i32, _i32]),
+    "mrec_ncf_topk": (ctypes.c_int, [ctypes.POINTER(NcfTopkArgs), _vp]),
     "mrec_tower_fwd_bwd": (ctypes.c_int, [ctypes.POINTER(TowerArgs), _vp]),
     "mrec_tower_image_elems": (ctypes.c_int64, [_i64, _i64, _i32]),
     "mrec_tower_weight_prep": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),

@@ -345,6 +345,55 @@ def topk(rows, dim: int, q, k: int, low: int, high: int, use_w: bool, exclude=No
     return topk_finish(best_s, best_i)
 
 
+def ncf_topk(tables, E: int, uid, weights, biases, wp, k: int, low: int, high: int, exclude=None,
+             chunk: int = 8192, round_bf16: bool = True):
+    """``mrec_ncf_topk`` in torch ops (include/mrec.h "NCF retrieval"): the k best items of
+    ``[low, high)`` per user under the NeuMF scorer, with layer 0 split as the kernel
+    splits it -- ``a = b_0 + W_0[:, :E] mlp_u`` once per user, ``c = W_0[:, E:] mlp_i`` once
+    per item, ``h_1 = relu(a + c)`` -- and ``mrec_topk``'s selection rules.  ``tables`` are
+    the four tables ``(mf_u, mf_i, mlp_u, mlp_i)`` as ``[rows, >= E]`` views on any device
+    (the item tables are read ``chunk`` rows at a time), ``weights`` / ``biases`` / ``wp``
+    as for ``ncf_score``, ``exclude`` an ``(offsets, items, rows)`` triple or None.  Chunked
+    over the items with a running merge (``topk_fold``); the chunk shrinks so that the
+    ``[B, chunk, width]`` activations stay small.  ``round_bf16`` applies the kernel's
+    rounding points (table elements, weight matrices, each h_l that feeds a layer);
+    False keeps fp32 throughout, which is what the CPU forward computes.  The ReLU is the
+    kernels' ``x > 0 ? x : 0``: a NaN pre-activation gives 0, so only a NaN in the MF term
+    makes a score NaN (and the item ineligible).
+    -> (ids int32 [B, k], scores float32 [B, k]) on uid's device."""
+    dev = uid.device
+    B = int(uid.shape[0])
+    r = bf16_round if round_bf16 else (lambda t: t)
+
+    def relu(x):
+        return torch.where(x > 0, x, torch.zeros_like(x))
+
+    mf_u, mf_i, mlp_u, mlp_i = tables
+    ws = [r(w.detach().float()).to(dev) for w in weights]
+    bs = [b.detach().float().to(dev) for b in biases]
+    wp = wp.detach().float().reshape(-1).to(dev)
+    idx = uid.to(device=mf_u.device, dtype=torch.int64)
+    mu = r(mf_u.detach()[idx, :E].float()).to(dev)
+    a = r(mlp_u.detach()[idx, :E].float()).to(dev) @ ws[0][:, :E].t() + bs[0]
+    best_s = torch.full((B, k), float("-inf"), dtype=torch.float32, device=dev)
+    best_i = torch.full((B, k), -1, dtype=torch.int64, device=dev)
+    pairs = None
+    if exclude is not None and B > 0:
+        pairs = topk_exclusion_pairs(exclude[0], exclude[1], exclude[2], B, dev)
+    widest = max([E] + [int(w.shape[0]) for w in ws])
+    chunk = max(1, min(int(chunk), (1 << 24) // max(1, B * widest)))
+    for c0 in range(low, high, chunk):
+        c1 = min(high, c0 + chunk)
+        g = mu.unsqueeze(1) * r(mf_i.detach()[c0:c1, :E].float()).to(dev).unsqueeze(0)
+        c = r(mlp_i.detach()[c0:c1, :E].float()).to(dev) @ ws[0][:, E:].t()
+        h = relu(a.unsqueeze(1) + c.unsqueeze(0))
+        for w, b in zip(ws[1:], bs[1:]):
+            h = relu(r(h) @ w.t() + b)
+        s = g @ wp[:E] + h @ wp[E:]
+        best_s, best_i = topk_fold(best_s, best_i, s, c0, pairs)
+    return topk_finish(best_s, best_i)
+
+
 def topk_fold(best_s, best_i, s, c0: int, pairs=None):
     """Fold the scores ``s [B, n]`` of items ``c0 .. c0 + n - 1`` into the running lists
     ``(best_s, best_i) [B, k]`` of a scan in ascending id order.  NaN scores and the

@@ -15,23 +15,13 @@
 // C/D map (col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)) leaves the 16
 // scores of ONE query in a lane's registers, so the query's threshold is one register.
 //
-// Selection.  A candidate is the 64-bit key
-//   [ordered bits of the score (-0.0 folded into +0.0) | 0xffffffff - id]
-// whose unsigned order IS the total order (bigger = better), and whose value is unique per
-// item: the k largest keys of a set do not depend on the order the set was built in.  Per
-// query the workgroup keeps an LDS buffer of `cap` keys, a count and a threshold (the
-// k-th best key after the last reduction, 0 before there are k).  A lane whose score
-// reaches the threshold's score forms the key, and if it beats the threshold looks the
-// item up in the query's exclusion list (binary search) and appends it (LDS atomic on the
-// count).  When a count passes `lim` = cap - TK_TI (a tile can add TK_TI keys to a query at
-// the most) every buffer is sorted (a bitonic network over all queries at once, padded
-// virtually to a power of two), cut to k, and the thresholds are raised.  A split ends
-// with the same reduction and writes its k keys per query: decoded straight into the
-// output when there is one split, else as keys into the workspace [B, splits, k], which
-// phase 2 (one workgroup per query) sorts again and decodes.  Every item of the true top
-// k passes every threshold, whatever the geometry, so the result is a function of the
-// inputs alone.
+// Selection (topk_select.h, shared with ncf_topk.hip): per query an LDS buffer of `cap`
+// 64-bit keys, a count and a threshold; a lane whose score reaches the threshold's score
+// offers the item (exclusion lookup, LDS append), and when a count passes `lim` = cap - TK_TI
+// (a tile can add TK_TI keys to a query at the most) every buffer is sorted, cut to k, and
+// the thresholds are raised.  The result is a function of the inputs alone.
 #include "common.h"
+#include "topk_select.h"
 
 namespace mrec {
 
@@ -40,11 +30,7 @@ typedef float tk_f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int TK_TQ = 32;        // queries per workgroup
 constexpr int TK_TI = 128;       // items per streamed tile: 32 per wave
-constexpr int TK_THREADS = 256;
 constexpr int TK_PF = 3;         // tiles in flight per wave
-constexpr int TK_MAXK = 128;
-constexpr int TK_MAX_SPLITS = 64;
-constexpr int TK_MERGE_MAX = TK_MAX_SPLITS * TK_MAXK;  // keys phase 2 sorts in LDS
 
 struct TopkArgs {
   const char *table;  // the table's row 0 (bank data + row_offset[table] rows)
@@ -54,74 +40,15 @@ struct TopkArgs {
   const void *q;
   int64_t ldq;
   int32_t q_bf16;
-  int32_t batch;
-  int32_t k, cap, lim, P;  // buffer capacity, reduction trigger, pow2 >= cap
+  int32_t cap, lim, P;  // buffer capacity, reduction trigger, pow2 >= cap
   const int64_t *ex_off;
   const int32_t *ex_items;
   int64_t ex_rows;
   const void *ex_row;
   int32_t ex_row64;
-  int32_t splits, tiles_per_split;
-  unsigned long long *part;  // [batch, splits, k] keys (splits > 1)
-  int32_t *out_ids;
-  float *out_scores;
-  int64_t ld_out;
+  int32_t tiles_per_split;
+  TkOut o;
 };
-
-__device__ __forceinline__ uint32_t tk_ord(float s) {
-  const uint32_t u = __float_as_uint(s + 0.f);  // -0.0 + 0.0 = +0.0
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float tk_unord(uint32_t o) {
-  return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
-}
-__device__ __forceinline__ unsigned long long tk_key(float s, int32_t id) {
-  return (static_cast<unsigned long long>(tk_ord(s)) << 32) | (0xffffffffu - static_cast<uint32_t>(id));
-}
-// key -> (id, score); the empty key 0 and a score of -inf give (-1, -inf)
-__device__ __forceinline__ void tk_emit(unsigned long long key, int32_t *id, float *score) {
-  const float s = key ? tk_unord(static_cast<uint32_t>(key >> 32)) : -INFINITY;
-  *score = s;
-  *id = s == -INFINITY ? -1 : static_cast<int32_t>(0xffffffffu - static_cast<uint32_t>(key));
-}
-
-// Sort the first cnt[q] keys of each of nq buffers (buf + q * stride) descending, the
-// whole workgroup together.  A bitonic network whose comparators all point the same way
-// (the first step of a merge mirrors, the rest are half-cleaners): positions >= cnt[q]
-// stand for the smallest key and never move, so any count <= P works.  Ends at a barrier.
-__device__ __forceinline__ void tk_sort(unsigned long long *buf, int nq, int stride, const int *cnt,
-                                        int P, int tid) {
-  const int half = P >> 1;
-  const int hs = __builtin_ctz(half);
-  for (int size = 2; size <= P; size <<= 1) {
-    for (int st = size >> 1; st > 0; st >>= 1) {
-      const bool mirror = st == (size >> 1);
-      // four comparators per thread and round, all their reads before any write (the
-      // comparators of a step touch disjoint slots): four LDS round trips overlap
-      for (int idx0 = tid; idx0 < nq * half; idx0 += 4 * TK_THREADS) {
-        unsigned long long *pi[4], *pj[4], x[4], y[4];
-        bool on[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int idx = idx0 + u * TK_THREADS;
-          const int qi = idx >> hs, p = idx & (half - 1);
-          const int t = p & (st - 1), base = (p - t) << 1;
-          const int i = base + t;
-          const int j = mirror ? base + size - 1 - t : i + st;
-          on[u] = idx < nq * half && j < cnt[idx < nq * half ? qi : 0];
-          pi[u] = buf + (on[u] ? qi * stride + i : 0);
-          pj[u] = buf + (on[u] ? qi * stride + j : 0);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) x[u] = *pi[u], y[u] = *pj[u];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-          if (on[u] && x[u] < y[u]) *pi[u] = y[u], *pj[u] = x[u];
-      }
-      __syncthreads();
-    }
-  }
-}
 
 // One K-step's A fragment of this lane from the raw 16-byte loads of its 8 elements (one
 // load of a bf16 row, two of an fp32 row: rounded here, at use, so that a fetched tile
@@ -151,7 +78,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_scan_kernel(TopkArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
   const int64_t qrow = static_cast<int64_t>(blockIdx.x) * TK_TQ + r;  // this lane's query
-  const bool qlive = qrow < p.batch;
+  const bool qlive = qrow < p.o.batch;
   const bool klive = 8 * h < D;  // (D = 8: the upper half of the K-step is padding)
   if (tid < TK_TQ) cnt[tid] = 0, thr[tid] = 0;
 
@@ -234,90 +161,19 @@ __global__ __launch_bounds__(TK_THREADS) void topk_scan_kernel(TopkArgs p) {
       }
     }
     const unsigned long long th = thr[r];
-    const float th_s = th ? tk_unord(static_cast<uint32_t>(th >> 32)) : -INFINITY;
+    const float th_s = tk_thr_score(th);
     int full = 0;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const float s = acc[e];
-      if (s >= th_s) {  // (false for a NaN)
-        const int64_t item = item0 + (e & 3) + 8 * (e >> 2);
-        if (qlive && item < p.high) {
-          const int32_t id = static_cast<int32_t>(item);
-          const unsigned long long key = tk_key(s, id);
-          if (key > th) {
-            int64_t lo = ex_lo, hi = ex_hi;  // lower bound of id
-            while (lo < hi) {
-              const int64_t mid = lo + ((hi - lo) >> 1);
-              if (p.ex_items[mid] < id)
-                lo = mid + 1;
-              else
-                hi = mid;
-            }
-            if (!(lo < ex_hi && p.ex_items[lo] == id)) {
-              const int slot = atomicAdd(&cnt[r], 1);
-              if (slot < p.cap) buf[r * p.cap + slot] = key;  // (always: cnt <= lim before the tile)
-              full |= slot + 1 > p.lim;
-            }
-          }
-        }
-      }
+      const int64_t item = item0 + (e & 3) + 8 * (e >> 2);
+      if (qlive && item < p.high)
+        full |= tk_offer(acc[e], static_cast<int32_t>(item), th, th_s, p.ex_items, ex_lo, ex_hi, buf, cnt, r,
+                         p.cap, p.lim);
     }
-    if (__syncthreads_or(full)) {
-      tk_sort(buf, TK_TQ, p.cap, cnt, p.P, tid);
-      if (tid < TK_TQ && cnt[tid] >= p.k) {
-        thr[tid] = buf[tid * p.cap + p.k - 1];
-        cnt[tid] = p.k;
-      }
-      __syncthreads();
-    }
+    if (__syncthreads_or(full)) tk_cut(buf, thr, cnt, TK_TQ, p.cap, p.o.k, p.P, tid);
   }
   // the split's k best of every query
-  tk_sort(buf, TK_TQ, p.cap, cnt, p.P, tid);
-  for (int i = tid; i < TK_TQ * p.k; i += TK_THREADS) {
-    const int qi = i / p.k, j = i - qi * p.k;
-    const int64_t b = static_cast<int64_t>(blockIdx.x) * TK_TQ + qi;
-    if (b >= p.batch) continue;
-    const unsigned long long key = j < cnt[qi] ? buf[qi * p.cap + j] : 0ull;
-    if (p.splits > 1) {
-      p.part[(b * p.splits + blockIdx.y) * p.k + j] = key;
-    } else {
-      int32_t id;
-      float s;
-      tk_emit(key, &id, &s);
-      p.out_ids[b * p.ld_out + j] = id;
-      p.out_scores[b * p.ld_out + j] = s;
-    }
-  }
-}
-
-// Phase 2: the splits' lists of one query, sorted together; the first k decoded.
-__global__ __launch_bounds__(TK_THREADS) void topk_merge_kernel(TopkArgs p, int P) {
-  extern __shared__ __attribute__((aligned(16))) char tk_lds[];
-  unsigned long long *buf = reinterpret_cast<unsigned long long *>(tk_lds);  // [P]
-  __shared__ int n_sh;
-  const int tid = threadIdx.x;
-  const int64_t b = blockIdx.x;
-  const int n = p.splits * p.k;
-  for (int i = tid; i < n; i += TK_THREADS) buf[i] = p.part[b * n + i];
-  if (tid == 0) n_sh = n;
-  __syncthreads();
-  tk_sort(buf, 1, P, &n_sh, P, tid);
-  for (int j = tid; j < p.k; j += TK_THREADS) {
-    int32_t id;
-    float s;
-    tk_emit(buf[j], &id, &s);
-    p.out_ids[b * p.ld_out + j] = id;
-    p.out_scores[b * p.ld_out + j] = s;
-  }
-}
-
-// an empty range: every slot is padding
-__global__ __launch_bounds__(TK_THREADS) void topk_fill_kernel(TopkArgs p) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * TK_THREADS + threadIdx.x;
-  if (i >= static_cast<int64_t>(p.batch) * p.k) return;
-  const int64_t b = i / p.k, j = i - b * p.k;
-  p.out_ids[b * p.ld_out + j] = -1;
-  p.out_scores[b * p.ld_out + j] = -INFINITY;
+  tk_finish(buf, cnt, TK_TQ, p.cap, p.P, static_cast<int64_t>(blockIdx.x) * TK_TQ, blockIdx.y, p.o, tid);
 }
 
 }  // namespace mrec
@@ -325,24 +181,6 @@ __global__ __launch_bounds__(TK_THREADS) void topk_fill_kernel(TopkArgs p) {
 using namespace mrec;
 
 namespace {
-
-int tk_cus() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      v = 256;
-    (void)hipGetLastError();
-    return v;
-  }();
-  return n;
-}
-
-int tk_pow2_at_least(int v) {
-  int p = 2;
-  while (p < v) p <<= 1;
-  return p;
-}
 
 bool tk_dim_ok(int32_t D) { return D == 8 || D == 16 || D == 32 || D == 64; }
 
@@ -391,9 +229,7 @@ int32_t mrec_topk_splits(int64_t batch, int64_t n_items) {
 }
 
 size_t mrec_topk_workspace_size(int64_t batch, int32_t k, int32_t splits) {
-  if (batch <= 0 || k <= 0 || splits < 0 || splits == 1) return 0;
-  if (splits == 0 || splits > TK_MAX_SPLITS) splits = TK_MAX_SPLITS;
-  return static_cast<size_t>(batch) * splits * k * sizeof(unsigned long long);
+  return tk_workspace_size(batch, k, splits);
 }
 
 mrec_status mrec_topk(const mrec_topk_args *a, mrec_stream stream) {
@@ -447,8 +283,8 @@ mrec_status mrec_topk(const mrec_topk_args *a, mrec_stream stream) {
   p.q = a->q;
   p.ldq = a->ldq;
   p.q_bf16 = a->q_dtype == MREC_BF16;
-  p.batch = static_cast<int32_t>(a->batch);
-  p.k = a->k;
+  p.o.batch = static_cast<int32_t>(a->batch);
+  p.o.k = a->k;
   p.lim = 2 * a->k > 64 ? 2 * a->k : 64;
   p.cap = p.lim + TK_TI;
   p.P = tk_pow2_at_least(p.cap);
@@ -457,19 +293,16 @@ mrec_status mrec_topk(const mrec_topk_args *a, mrec_stream stream) {
   p.ex_rows = a->excl_n_rows;
   p.ex_row = a->excl_row;
   p.ex_row64 = a->excl_row_dtype == MREC_I64;
-  p.out_ids = a->out_ids;
-  p.out_scores = a->out_scores;
-  p.ld_out = a->ld_out;
+  p.o.out_ids = a->out_ids;
+  p.o.out_scores = a->out_scores;
+  p.o.ld_out = a->ld_out;
+  p.o.splits = 1;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (n_items == 0) {
-    const int64_t total = a->batch * a->k;
-    topk_fill_kernel<<<dim3(static_cast<unsigned>((total + TK_THREADS - 1) / TK_THREADS)), TK_THREADS, 0, s>>>(p);
-    return launch_status("mrec_topk");
-  }
+  if (n_items == 0) return tk_launch_fill(p.o, s, "mrec_topk");
   const int64_t n_tiles = (n_items + TK_TI - 1) / TK_TI;
-  p.splits = splits;
+  p.o.splits = splits;
   p.tiles_per_split = static_cast<int32_t>((n_tiles + splits - 1) / splits);
-  p.part = static_cast<unsigned long long *>(a->workspace);
+  p.o.part = static_cast<unsigned long long *>(a->workspace);
   const dim3 grid(static_cast<unsigned>((a->batch + TK_TQ - 1) / TK_TQ), static_cast<unsigned>(splits));
   const size_t lds = static_cast<size_t>(TK_TQ) * p.cap * 8 + TK_TQ * (8 + 4);
   if (bank->dtype == MREC_BF16)
@@ -478,16 +311,7 @@ mrec_status mrec_topk(const mrec_topk_args *a, mrec_stream stream) {
     tk_launch_dim<float>(bank->dim, p, grid, lds, s);
   mrec_status st = launch_status("mrec_topk");
   if (st != MREC_OK || splits == 1) return st;
-  static const int once = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(topk_merge_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, TK_MERGE_MAX * 8);
-    (void)hipGetLastError();
-    return 1;
-  }();
-  (void)once;
-  const int P2 = tk_pow2_at_least(splits * a->k);
-  topk_merge_kernel<<<dim3(static_cast<unsigned>(a->batch)), TK_THREADS, static_cast<size_t>(P2) * 8, s>>>(p, P2);
-  return launch_status("mrec_topk");
+  return tk_launch_merge(p.o, s, "mrec_topk");
 }
 
 }  // extern "C"

@@ -33,9 +33,17 @@ Checkpoint compatibility: ``state_dict`` / ``load_state_dict`` speak the referen
 ``IModel._reset_weights_fn`` in registration order), so the same ``random_seed`` gives
 bit-identical parameters (golden G17).
 
-``recommend`` (full-catalogue top-k) runs the generic path of ``IModel``: the item range
-goes through ``forward`` in chunks of candidates.  The scorer is an MLP over the pair,
-not a dot product with an item row, so the fused retrieval kernel does not apply.
+``recommend`` (full-catalogue top-k): the scorer is an MLP over the pair, not a dot
+product with an item row, so there is no ``_retrieval_query``.  On a GPU, for the shapes
+``retrieval.ncf_supported`` names, it is ``retrieval.ncf_topk`` -- one ``mrec_ncf_topk``
+launch (csrc/ncf_topk.hip) that forms the (user, item) pairs on chip, with layer 0 split
+into a per-user and a per-item half, and selects the k best without a gathered row or a
+``[B, items]`` score reaching memory.  The kernel's LDS plan holds every layer's weight
+image and the per-user key buffers at once, so wide towers -- (64, [128, 128, 128]), most
+three-layer towers of widths near 100 at emb_size 64 -- are outside it.  On a CPU, for any
+other shape, and with
+``retrieval.NCF_TOPK_FUSED = False`` it is ``IModel.recommend_by_forward``: the item
+range goes through ``forward`` in chunks of candidates.
 """
 from typing import Any, Dict, List
 
@@ -49,6 +57,7 @@ from pytorchrec_amd.model.DeepFM import _parse_layers
 from pytorchrec_amd.model.IModel import IModel
 from pytorchrec_amd.model.layer.MLP import MLP
 from pytorchrec_amd.utils.argument import ArgumentDescription
+from pytorchrec_amd.utils.data_structure import tensor_to_device
 
 _BANK_KEY = "embeddings.weight"
 _TABLE_KEYS = ("mf_u_embeddings.weight", "mf_i_embeddings.weight", "mlp_u_embeddings.weight",
@@ -162,7 +171,7 @@ class NCF(IModel):
             self.mlp.to(self.build_device)
             self.prediction.to(self.build_device)
 
-    candidate_lists = True  # (recommend: IModel's generic path, see the module docstring)
+    candidate_lists = True  # (recommend_by_forward applies; see the module docstring)
 
     def forward(self, data: Dict[str, Tensor]):
         u_ids = self.uid_column.get_feature_ids(data)
@@ -181,3 +190,25 @@ class NCF(IModel):
         target = torch.zeros_like(prediction, dtype=torch.float32)
         target[:, 0] = 1
         return prediction, target
+
+    def recommend(self, data: Dict[str, Tensor], k: int, *, exclude=None, low=None, high=None):
+        """``IModel.recommend``'s contract.  The fused kernel on a GPU when it covers the
+        shape (``retrieval.ncf_topk``), else ``recommend_by_forward``.  Runs in eval mode
+        (no dropout) under ``no_grad`` and restores the training flag."""
+        from pytorchrec_amd import retrieval
+        bank = self.embeddings
+        dense = [p for p in self.parameters() if p is not bank.weight]
+        if not (retrieval.NCF_TOPK_FUSED and bank.weight.is_cuda and isinstance(k, int)
+                and all(p.is_cuda and p.dtype == torch.float32 for p in dense)
+                and retrieval.ncf_supported(self.emb_size, self.layers, k, bank.weight.dtype)):
+            return self.recommend_by_forward(data, k, exclude=exclude, low=low, high=high)
+        low, high = self._retrieval_range(low, high)
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                data = tensor_to_device(data, self._model_device())
+                uid = self.uid_column.get_feature_ids(data).reshape(-1)
+                return retrieval.ncf_topk(self, uid, k, low=low, high=high, exclude=exclude)
+        finally:
+            self.train(was_training)
