@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MREC_ABI_VERSION 36
+#define MREC_ABI_VERSION 37
 #define MREC_MAX_TABLES 64      /* tables per table bank / per call */
 #define MREC_BWD_MAX_BATCH 8192  /* lookups per table per plan/apply call */
 #define MREC_BWD_HASH_MAX_BATCH 4096  /* batches up to this use the hash plan */
@@ -1789,6 +1789,120 @@ int32_t mrec_ncf_topk_tile_items(void); /* items per streamed tile   */
 int32_t mrec_ncf_topk_splits(int64_t batch, int64_t n_items); /* the default item-split count */
 size_t mrec_ncf_topk_workspace_size(int64_t batch, int32_t k, int32_t splits);
 mrec_status mrec_ncf_topk(const mrec_ncf_topk_args *args, mrec_stream stream);
+
+/* ------------------------------------------------------------------------- */
+/* Shared negatives: list-wise losses over one pool of negatives shared by the */
+/* batch, loss and gradients fused with the scores (ABI 37; csrc/shneg.hip)    */
+/* ------------------------------------------------------------------------- */
+/*
+ * Inputs.  q [batch, D] (q_dtype MREC_F32 or MREC_BF16, row stride ldq elements), the
+ * gathered item rows pos [batch, D] and neg [n_neg, D] of ONE dtype (row_dtype MREC_F32 or
+ * MREC_BF16; row strides ld_pos, ld_neg); neg may alias pos (in-batch negatives).  Optional
+ * pos_id [batch] and neg_id [n_neg] (id_dtype MREC_I32 or MREC_I64, both NULL or both
+ * given): candidate j is MASKED for query b iff neg_id[j] == pos_id[b]; without ids nothing
+ * is masked.  Optional pos_bias [batch], neg_bias [n_neg]: fp32 constants added to the
+ * scores (the log-Q correction); they get no gradient.
+ *   s[b, j] = sum_d bf16(q[b, d]) * bf16(neg[j, d]) (+ neg_bias[j])
+ *   s+[b]   = sum_d bf16(q[b, d]) * bf16(pos[b, d]) (+ pos_bias[b])
+ * bf16() is round-to-nearest-even (mrec_topk's operand rounding: exact for bf16 operands),
+ * every product accumulates in fp32 (s through the MFMA, s+ as an fmaf chain).  E_b is the
+ * set of unmasked candidates of query b, n_b = |E_b|.  Per-query loss (kind):
+ *   MREC_SHNEG_SOFTMAX  L_b = log(exp(s+[b]) + sum_{j in E_b} exp(s[b, j])) - s+[b]
+ *                       an online log-sum-exp with a running maximum: safe for scores of
+ *                       any magnitude
+ *   MREC_SHNEG_BPR      L_b = (1 / n_b) sum_{j in E_b} softplus(s[b, j] - s+[b])
+ *                       (mrec_pair_loss_fwd's MREC_PAIR_BPR of each pair, averaged)
+ *   MREC_SHNEG_TOP1     L_b = (1 / n_b) sum_{j in E_b} sigmoid(s[b, j] - s+[b]) + sigmoid(s[b, j]^2)
+ *                       (MREC_PAIR_TOP1 in the same way)
+ * n_b = 0 (n_neg = 0 included) gives L_b = 0 and zero gradients for every kind; batch = 0
+ * launches nothing and writes nothing.  reduction: MREC_REDUCE_NONE writes loss [batch];
+ * MEAN / SUM write loss [1], a fixed-order reduction of the L_b (one workgroup, as
+ * mrec_pair_loss_fwd), the L_b themselves going through the workspace.
+ *   The forward also writes stats [batch][4] fp32 -- s+[b], the maximum M_b over s+[b] and
+ * the unmasked s[b, j], the sum exp(s+ - M_b) + sum_j exp(s[b, j] - M_b) (softmax only), n_b
+ * -- which is all the backward keeps: it recomputes every score tile with the same MFMAs.
+ * Gradients, with g the upstream gradient on the device ([batch] for NONE, [1] otherwise;
+ * g_b = g[b], g[0] / batch or g[0]) and c_b = g_b / sum_b (softmax) or g_b / n_b (bpr, top1):
+ *   a[b, j] = g_b dL_b/ds[b, j]   softmax exp(s[b, j] - M_b) c_b;  bpr softplus'(x) c_b;
+ *                                 top1 (sigmoid'(x) + 2 s[b, j] sigmoid'(s[b, j]^2)) c_b;
+ *                                 x = s[b, j] - s+[b];  0 where masked
+ *   a[b, +] = g_b dL_b/ds+[b]     softmax exp(s+[b] - M_b) c_b - g_b;  bpr, top1 minus the
+ *                                 fp32 sum over j of the first term of a[b, j]
+ *   dq[b]   = sum_j a[b, j] bf16(neg[j]) + a[b, +] bf16(pos[b])       in q's dtype
+ *   dpos[b] = a[b, +] bf16(q[b])                                      in the rows' dtype
+ *   dneg[j] = sum_b a[b, j] bf16(q[b])                                in the rows' dtype
+ * Rounding points: each a[b, j] enters the MFMAs of the two sums over j and over b as
+ * hi + lo, two bf16 values (hi = bf16(a), lo = bf16(a - hi): 2^-16 relative each; a
+ * coefficient that is a bf16 value is exact); a[b, +] and the products with it stay fp32; every sum accumulates in fp32 and each output is rounded once.  A candidate that is
+ * masked for every query contributes exactly nothing, whatever its row holds (its row is
+ * replaced by zeros where no coefficient of a 32 x 32 tile uses it), and its dneg is 0; a
+ * non-finite row that some query does use may reach the gradients of its tile's queries.
+ *   Determinism.  The outputs are a function of the inputs alone: no floating-point
+ * atomics, every sum in a fixed order (per 1024 streamed rows one MFMA chain per wave, the
+ * four waves in order, then the chunks of 1024 in order).  `splits` cuts the batch of the
+ * candidate-major pass (dneg) into parts run by different workgroups, 0 =
+ * mrec_shneg_splits(batch, n_neg), at most 64: it moves whole chunks only, their partials
+ * go through `workspace` and are summed in the same order, so the bits do not depend on
+ * it, on the grid, on where the operands lie or on the run.
+ *   workspace: 16-byte aligned, mrec_shneg_workspace_size(batch, n_neg, D, splits) bytes
+ * (splits = 0 there sizes for any default); used by the forward for MEAN / SUM and by the
+ * backward when more than one split runs.  One description for both directions: the forward
+ * ignores g and the gradients' fields, the backward ignores loss.
+ * Compiled shapes (mrec_shneg_supported): D in {8, 16, 32, 64}, q and rows F32 or BF16, any
+ * batch and n_neg up to 2^31 - 1.  q, pos and neg need 16-byte aligned rows (pointer and
+ * row stride in bytes multiples of 16); the outputs any row stride >= D.  A workgroup holds
+ * mrec_shneg_tile_queries() queries (forward, query-major pass) or
+ * mrec_shneg_tile_candidates() candidates (candidate-major pass).  Never read: columns >= D
+ * of any row; never written: columns >= D and rows past the shape.  Caller-owned buffers,
+ * no allocation, no host synchronisation, all work on `stream`; anything else is
+ * MREC_EINVAL with mrec_last_error() before any launch.
+ * mrec_shneg_math_probe applies one of the device functions the losses call to x [n] fp32
+ * -- fn 0 expf, 1 logf, 2 softplus, 3 sigmoid, 4 sigmoid' -- so that their error can be
+ * measured alone (the tests' tolerance).
+ */
+typedef enum { MREC_SHNEG_SOFTMAX = 0, MREC_SHNEG_BPR = 1, MREC_SHNEG_TOP1 = 2 } mrec_shneg_kind;
+
+typedef struct {
+  const void *q;
+  mrec_dtype q_dtype;
+  int64_t ldq;
+  const void *pos;
+  int64_t ld_pos;
+  const void *neg;
+  int64_t ld_neg;
+  mrec_dtype row_dtype;
+  int64_t batch;
+  int64_t n_neg;
+  int32_t D;
+  const void *pos_id;
+  const void *neg_id;
+  mrec_dtype id_dtype;
+  const float *pos_bias;
+  const float *neg_bias;
+  int32_t kind;
+  int32_t reduction;
+  float *loss;
+  float *stats;
+  const float *g;
+  void *dq;
+  int64_t ld_dq;
+  void *dpos;
+  int64_t ld_dpos;
+  void *dneg;
+  int64_t ld_dneg;
+  int32_t splits;
+  void *workspace;
+  size_t workspace_bytes;
+} mrec_shneg_args;
+
+int32_t mrec_shneg_supported(int32_t D, mrec_dtype q_dtype, mrec_dtype row_dtype);
+int32_t mrec_shneg_tile_queries(void);    /* queries a workgroup holds    */
+int32_t mrec_shneg_tile_candidates(void); /* candidates a workgroup holds */
+int32_t mrec_shneg_splits(int64_t batch, int64_t n_neg); /* the default batch-split count */
+size_t mrec_shneg_workspace_size(int64_t batch, int64_t n_neg, int32_t D, int32_t splits);
+mrec_status mrec_shneg_loss_fwd(const mrec_shneg_args *args, mrec_stream stream);
+mrec_status mrec_shneg_loss_bwd(const mrec_shneg_args *args, mrec_stream stream);
+mrec_status mrec_shneg_math_probe(int32_t fn, const float *x, int64_t n, float *y, mrec_stream stream);
 
 #ifdef __cplusplus
 }

@@ -20,7 +20,7 @@ import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("MREC_LIB_PATH") or os.path.join(LIB_DIR, "libmrec.so")
 
-ABI_VERSION = 36
+ABI_VERSION = 37
 MAX_TABLES = 64
 BWD_MAX_BATCH = 8192
 BWD_HASH_MAX_BATCH = 4096  # batches up to this use the hash plan (fusable into a GEMM launch)
@@ -43,6 +43,8 @@ POOL_PAD_ZERO, POOL_PAD_NEGATIVE = 0, 1
 PAIR_BPR, PAIR_TOP1 = 0, 1
 REDUCE_NONE, REDUCE_MEAN, REDUCE_SUM = 0, 1, 2
 NEG_MAX_ATTEMPTS = 32
+# shared negatives (mrec_shneg_loss_*)
+SHNEG_SOFTMAX, SHNEG_BPR, SHNEG_TOP1 = 0, 1, 2
 
 _STATUS_NAMES = {OK: "MREC_OK", EINVAL: "MREC_EINVAL", EOOB: "MREC_EOOB", EHIP: "MREC_EHIP",
                  ERCCL: "MREC_ERCCL", ENOSPC: "MREC_ENOSPC"}
@@ -290,6 +292,23 @@ class NcfTopkArgs(ctypes.Structure):
                 ("ld_out", ctypes.c_int64)]
 
 
+class ShnegArgs(ctypes.Structure):
+    """mrec_shneg_args (include/mrec.h, ABI 37): one description for both directions."""
+    _fields_ = [("q", ctypes.c_void_p), ("q_dtype", ctypes.c_int), ("ldq", ctypes.c_int64),
+                ("pos", ctypes.c_void_p), ("ld_pos", ctypes.c_int64),
+                ("neg", ctypes.c_void_p), ("ld_neg", ctypes.c_int64), ("row_dtype", ctypes.c_int),
+                ("batch", ctypes.c_int64), ("n_neg", ctypes.c_int64), ("D", ctypes.c_int32),
+                ("pos_id", ctypes.c_void_p), ("neg_id", ctypes.c_void_p), ("id_dtype", ctypes.c_int),
+                ("pos_bias", ctypes.c_void_p), ("neg_bias", ctypes.c_void_p),
+                ("kind", ctypes.c_int32), ("reduction", ctypes.c_int32),
+                ("loss", ctypes.c_void_p), ("stats", ctypes.c_void_p), ("g", ctypes.c_void_p),
+                ("dq", ctypes.c_void_p), ("ld_dq", ctypes.c_int64),
+                ("dpos", ctypes.c_void_p), ("ld_dpos", ctypes.c_int64),
+                ("dneg", ctypes.c_void_p), ("ld_dneg", ctypes.c_int64),
+                ("splits", ctypes.c_int32),
+                ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
 LAYOUT_ROW, LAYOUT_COL = 0, 1
 ACT_NONE, ACT_RELU = 0, 1
 
@@ -493,6 +512,14 @@ SIGNATURES = {
     "mrec_ncf_topk_splits": (ctypes.c_int32, [_i64, _i64]),
     "mrec_ncf_topk_workspace_size": (ctypes.c_size_t, [_i64, _i32, _i32]),
     "mrec_ncf_topk": (ctypes.c_int, [ctypes.POINTER(NcfTopkArgs), _vp]),
+    "mrec_shneg_supported": (ctypes.c_int32, [_i32, ctypes.c_int, ctypes.c_int]),
+    "mrec_shneg_tile_queries": (ctypes.c_int32, []),
+    "mrec_shneg_tile_candidates": (ctypes.c_int32, []),
+    "mrec_shneg_splits": (ctypes.c_int32, [_i64, _i64]),
+    "mrec_shneg_workspace_size": (ctypes.c_size_t, [_i64, _i64, _i32, _i32]),
+    "mrec_shneg_loss_fwd": (ctypes.c_int, [ctypes.POINTER(ShnegArgs), _vp]),
+    "mrec_shneg_loss_bwd": (ctypes.c_int, [ctypes.POINTER(ShnegArgs), _vp]),
+    "mrec_shneg_math_probe": (ctypes.c_int, [_i32, _vp, _i64, _vp, _vp]),
     "mrec_tower_fwd_bwd": (ctypes.c_int, [ctypes.POINTER(TowerArgs), _vp]),
     "mrec_tower_image_elems": (ctypes.c_int64, [_i64, _i64, _i32]),
     "mrec_tower_weight_prep": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),

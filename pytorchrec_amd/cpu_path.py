@@ -11,7 +11,9 @@ numpy.  ``sasrec_encode`` is the SASRec encoder in torch ops: the CPU path, and 
 the layered path for the shapes and modes the fused kernels do not cover
 (``dense.sasrec_encode`` decides); ``gru_encode`` is the same for the GRU4Rec recurrence
 (``dense.gru_encode`` decides).  ``topk`` is ``mrec_topk``, the full-catalogue retrieval, in
-torch ops, chunked over the items (``retrieval.topk`` decides).
+torch ops, chunked over the items (``retrieval.topk`` decides).  ``shared_negative_loss`` is
+``mrec_shneg_loss_fwd`` / ``_bwd``, the list-wise losses over a shared pool of negatives, in
+differentiable torch ops (``loss.SharedNegativeLoss`` decides).
 """
 from __future__ import annotations
 
@@ -417,3 +419,57 @@ def topk_finish(best_s, best_i):
     """-> (ids int32, scores float32): a slot whose score is -inf is padding, id -1."""
     best_i = torch.where(best_s == float("-inf"), torch.full_like(best_i, -1), best_i)
     return best_i.to(torch.int32), best_s
+
+
+SHNEG_KINDS = ("softmax", "bpr", "top1")
+
+
+def shared_negative_loss(q, pos, neg, kind: str, reduction: str = "mean", pos_id=None, neg_id=None,
+                         pos_bias=None, neg_bias=None, round_bf16: bool = False):
+    """``mrec_shneg_loss_fwd`` / ``_bwd`` in differentiable torch ops (include/mrec.h "Shared
+    negatives"): every query ``q [B, D]`` ranked against its own positive row ``pos [B, D]``
+    and one pool ``neg [S, D]`` shared by the batch; candidate j is masked for query b iff
+    ``neg_id[j] == pos_id[b]``; the biases are constants added to the scores (no gradient).
+    Arithmetic in fp32 (fp64 operands stay fp64), which is what the models' CPU forward
+    computes; ``round_bf16`` rounds q and the rows to bf16 first, the kernel's operands (a
+    GPU shape the kernel does not cover).  A candidate masked for every query is replaced
+    by zeros, so whatever its row holds it changes nothing and gets a zero gradient.
+    -> ``[B]`` for ``none``, else a scalar."""
+    if kind not in SHNEG_KINDS:
+        raise ValueError(f"kind must be one of {SHNEG_KINDS}, got {kind!r}")
+    if reduction not in ("none", "mean", "sum"):
+        raise ValueError(f"reduction参数不合法: {reduction}")
+    if (pos_id is None) != (neg_id is None):
+        raise ValueError("pos_id and neg_id go together")
+    dt = torch.float64 if q.dtype == torch.float64 else torch.float32
+    qf, pf, nf = q.to(dt), pos.to(dt), neg.to(dt)
+    if round_bf16:
+        qf, pf, nf = bf16_round(qf), bf16_round(pf), bf16_round(nf)
+    B, S = qf.shape[0], nf.shape[0]
+    if pos_id is not None:
+        mask = neg_id.reshape(1, S).to(torch.int64) == pos_id.reshape(B, 1).to(torch.int64)
+        if B:
+            nf = torch.where(mask.all(0).unsqueeze(1), torch.zeros_like(nf), nf)
+    else:
+        mask = torch.zeros(B, S, dtype=torch.bool, device=qf.device)
+    s = qf @ nf.t()
+    sp = (qf * pf).sum(1)
+    if neg_bias is not None:
+        s = s + neg_bias.detach().to(dt).reshape(1, S)
+    if pos_bias is not None:
+        sp = sp + pos_bias.detach().to(dt).reshape(B)
+    s = torch.where(mask, torch.zeros_like(s), s)  # (a masked score is never looked at)
+    n = (~mask).sum(1)
+    if kind == "softmax":
+        logits = torch.cat([sp.unsqueeze(1), s.masked_fill(mask, float("-inf"))], dim=1)
+        loss = torch.logsumexp(logits, dim=1) - sp
+    else:
+        x = s - sp.unsqueeze(1)
+        if kind == "bpr":
+            t = torch.nn.functional.softplus(x)
+        else:
+            t = torch.sigmoid(x) + torch.sigmoid(s * s)
+        loss = torch.where(mask, torch.zeros_like(t), t).sum(1) / n.clamp(min=1).to(dt)
+    if reduction == "none":
+        return loss
+    return loss.sum() / max(B, 1) if reduction == "mean" else loss.sum()

@@ -120,6 +120,29 @@ class FunkSVD(IModel):
         rows = gather(self.embeddings, [u_ids, torch.zeros_like(u_ids)], out_dtype=torch.float32)
         return rows[:, :self.emb_size], self.embeddings, 1, False, None
 
+    def _shared_negative_inputs(self, data: Dict[str, Tensor], neg_ids):
+        """Users, positives and the pool in ONE gather of the two-table bank: the pool's
+        slots of the user table's id list are padding (a zero row, no gradient), so every
+        row is looked up, and updated, once.  q is the user row, as in ``_retrieval_query``."""
+        u_ids = self.uid_column.get_feature_ids(data)
+        pos_ids = self._shared_positive_ids(data)
+        bank, D = self.embeddings, self.emb_size
+        B = u_ids.shape[0]
+        padded = bank.weight.is_cuda
+        i_ids = pos_ids.to(u_ids.dtype)
+        if neg_ids is not None:
+            S = neg_ids.shape[0]
+            # (the CPU gather has no padding slots: user row 0 stands in, its gradient is zero)
+            pad = torch.full((S,), -1 if padded else 0, dtype=u_ids.dtype, device=u_ids.device)
+            u_ids = torch.cat([u_ids, pad])
+            i_ids = torch.cat([i_ids, neg_ids.to(i_ids.dtype)])
+        if padded:  # a negative item id stays out of range (IndexError), never a padding slot
+            i_ids = torch.where(i_ids < 0, torch.full_like(i_ids, bank.category_nums[1]), i_ids)
+        rows = gather(bank, [u_ids, i_ids], out_dtype=torch.float32, pad_negative=padded)
+        pos_rows = rows[:B, D:2 * D]
+        neg_rows = rows[B:, D:2 * D] if neg_ids is not None else pos_rows
+        return rows[:B, :D], pos_rows, neg_rows, pos_ids
+
     def forward(self, data: Dict[str, Tensor]):
         u_ids = self.uid_column.get_feature_ids(data)
         i_ids = self.iid_column.get_feature_ids(data)

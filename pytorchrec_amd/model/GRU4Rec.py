@@ -151,6 +151,35 @@ class GRU4Rec(IModel):
         v = self._session_vector(rows.reshape(B, L, self.emb_size), his_len)
         return v.float(), bank, 0, False, None
 
+    def _lookup_rows(self, his: Tensor, his_len: Tensor, cand: Tensor) -> Tensor:
+        """History and candidate rows in ONE lookup (one sorted-segment backward, one update
+        per row, as a single nn.Embedding would do): ``[B L + len(cand), E]``, the history
+        first."""
+        bank = self.i_embeddings
+        act_dtype = torch.bfloat16 if bank.weight.is_cuda else torch.float32
+        hist_ids, padded = self._history_lookup_ids(his, his_len)
+        cand = cand.to(his.dtype)
+        if padded:
+            past = torch.full_like(his.reshape(-1)[:1], bank.category_nums[0])
+            cand = torch.where(cand < 0, past, cand)
+        return gather(bank, [torch.cat([hist_ids, cand])], out_dtype=act_dtype, pad_negative=padded)
+
+    def _shared_negative_inputs(self, data: Dict[str, Tensor], neg_ids):
+        """History, positives and the pool in the single lookup ``forward`` builds; q is the
+        session vector of ``_retrieval_query``, with gradients."""
+        his = self.his_column.get_feature_ids(data)
+        his_len = self.his_len_column.get_feature_ids(data)
+        if his.dim() != 2:
+            raise ValueError(f"his must be [B, L], got {tuple(his.shape)}")
+        pos_ids = self._shared_positive_ids(data)
+        B, L = his.shape
+        cand = pos_ids if neg_ids is None else torch.cat([pos_ids, neg_ids.to(pos_ids.dtype)])
+        rows = self._lookup_rows(his, his_len, cand)
+        v = self._session_vector(rows[:B * L].reshape(B, L, self.emb_size), his_len)
+        pos_rows = rows[B * L:B * L + B]
+        neg_rows = rows[B * L + B:] if neg_ids is not None else pos_rows
+        return v.float(), pos_rows, neg_rows, pos_ids
+
     def forward(self, data: Dict[str, Tensor]):
         i_ids = self.iid_column.get_feature_ids(data)
         his = self.his_column.get_feature_ids(data)
@@ -162,17 +191,7 @@ class GRU4Rec(IModel):
             raise ValueError(f"his must be [B, L], got {tuple(his.shape)}")
         B, N = i_ids.shape
         L, E = his.shape[1], self.emb_size
-        bank = self.i_embeddings
-        on_gpu = bank.weight.is_cuda
-        act_dtype = torch.bfloat16 if on_gpu else torch.float32
-        # history and candidate rows in ONE lookup (one sorted-segment backward, one
-        # update per row, as a single nn.Embedding would do)
-        hist_ids, padded = self._history_lookup_ids(his, his_len)
-        cand = i_ids.reshape(-1).to(his.dtype)
-        if padded:
-            past = torch.full_like(his.reshape(-1)[:1], bank.category_nums[0])
-            cand = torch.where(cand < 0, past, cand)
-        rows = gather(bank, [torch.cat([hist_ids, cand])], out_dtype=act_dtype, pad_negative=padded)
+        rows = self._lookup_rows(his, his_len, i_ids.reshape(-1))
         v = self._session_vector(rows[:B * L].reshape(B, L, E), his_len)
         prediction = (v.float().unsqueeze(1) * rows[B * L:].reshape(B, N, E).float()).sum(-1)
         target = None

@@ -29,6 +29,9 @@ MI355X additions (documented deviations):
   * ``set_negative_sampler``: pair-wise training draws its negatives per batch on
     the model's device (``sampling.NegativeSampler``) when the dataset has no
     ``train_neg_sample`` of its own (SimpleDataReader.py:280-300).
+  * ``set_shared_negatives``: list-wise training against ONE pool of negatives shared by
+    the batch (sampled, or the batch's own positives), for the dot-product models and a
+    ``loss.SharedNegativeLoss``; the ``[B, S]`` scores never exist on a GPU.
 """
 from __future__ import annotations
 
@@ -65,6 +68,7 @@ class IModel(Module, IWithArguments, ABC):
         self.compiled_metrics: Optional[list] = None
         self.compiled_device: Optional[torch.device] = None
         self._neg_sampler = None  # set_negative_sampler
+        self._shared_source = None  # set_shared_negatives
         self._init_weights()
         self._reset_weights()
 
@@ -434,6 +438,9 @@ class IModel(Module, IWithArguments, ABC):
         ``sampler=None`` turns it off."""
         if sampler is not None and int(n_neg) < 1:
             raise ValueError(f"n_neg must be >= 1, got {n_neg}")
+        if sampler is not None and self._shared_source is not None:
+            raise ValueError("shared negatives are set: per-row negatives and a shared pool "
+                             "exclude each other (set_shared_negatives(None) first)")
         ucol = uid_column if uid_column is not None else getattr(self, "uid_column", None)
         icol = iid_column if iid_column is not None else getattr(self, "iid_column", None)
         if sampler is not None and (ucol is None or icol is None):
@@ -456,6 +463,86 @@ class IModel(Module, IWithArguments, ABC):
             [pos.reshape(-1, 1), neg.to(device=pos.device, dtype=pos.dtype)], dim=1)
         return data
 
+    # -- shared negatives ---------------------------------------------------------
+    def set_shared_negatives(self, source, n_shared: Optional[int] = None, iid_column=None):
+        """Train every row of a batch against its own positive and ONE pool of negatives
+        shared by the whole batch (``loss.SharedNegativeLoss``: sampled softmax, or BPR /
+        Top1 averaged over the pool).  ``source``:
+          * a ``sampling.NegativeSampler``: the pool is ``n_shared`` plain draws of its
+            ``[low, high)`` per step -- ``sampler.sample(n_shared uids of -1, 1, step)``: a uid
+            outside the user range has an empty list, so nothing is rejected -- reproducible
+            from ``(seed, step)`` and identical on CPU and GPU;
+          * ``"in_batch"``: the pool is the batch's own positives (the same rows and ids are
+            passed as both sides; the mask removes each row's own positive and its duplicates);
+          * ``None``: off.
+        ``step`` is a host counter that advances once per ``train_step``.  A candidate equal
+        to a row's positive is masked for that row.  The model gathers history, positives
+        and pool in ONE lookup per bank (``_shared_negative_inputs``), so a row gets one
+        update per step.  Excludes ``set_negative_sampler``; ``train_step`` then requires the
+        compiled loss to be a ``SharedNegativeLoss``.  The item column defaults to
+        ``self.iid_column``; a ``[B, N]`` item column contributes its first entry, the
+        positive."""
+        if source is None:
+            self._shared_source = None
+            return
+        if type(self)._shared_negative_inputs is IModel._shared_negative_inputs:
+            raise NotImplementedError(f"{type(self).__name__} does not train with shared negatives")
+        if self._neg_sampler is not None:
+            raise ValueError("a negative sampler is set: per-row negatives and a shared pool "
+                             "exclude each other (set_negative_sampler(None) first)")
+        if isinstance(source, str):
+            if source != "in_batch":
+                raise ValueError(f"source must be a NegativeSampler, 'in_batch' or None, got {source!r}")
+            if n_shared is not None:
+                raise ValueError("in-batch negatives take their number from the batch: n_shared must be None")
+        else:
+            if not hasattr(source, "sample"):
+                raise ValueError(f"source must be a NegativeSampler, 'in_batch' or None, got {source!r}")
+            if n_shared is None or int(n_shared) < 1:
+                raise ValueError(f"a sampled pool needs n_shared >= 1, got {n_shared}")
+        icol = iid_column if iid_column is not None else getattr(self, "iid_column", None)
+        if icol is None:
+            raise ValueError("the model has no iid_column: pass it")
+        self._shared_source = source
+        self._shared_n = int(n_shared) if n_shared is not None else None
+        self._shared_column = icol
+        self._shared_step = 0
+
+    def shared_negative_pool(self, step: int) -> Optional[torch.Tensor]:
+        """The pool of step ``step``: item ids ``[n_shared]``, or None for in-batch negatives."""
+        src = self._shared_source
+        if isinstance(src, str):
+            return None
+        uids = torch.full((self._shared_n,), -1, dtype=torch.int64, device=src.device)
+        return src.sample(uids, 1, step=step).reshape(-1)
+
+    def _shared_negative_inputs(self, data: Dict, neg_ids: Optional[torch.Tensor]):
+        """A dot-product model returns ``(q [B, D], pos_rows [B, D], neg_rows [S, D], pos_ids
+        [B])`` from ONE gather per bank: q as ``_retrieval_query`` computes it, with
+        gradients and dropout as in ``forward``; ``neg_ids`` None means in-batch negatives
+        (``neg_rows`` is ``pos_rows`` itself)."""
+        raise NotImplementedError
+
+    def _shared_positive_ids(self, data: Dict) -> torch.Tensor:
+        pos = self._shared_column.get_feature_ids(data)
+        return pos[:, 0] if pos.dim() == 2 else pos
+
+    def _shared_negative_loss(self, data: Dict):
+        from pytorchrec_amd.loss import SharedNegativeLoss
+        if not isinstance(self.compiled_loss, SharedNegativeLoss):
+            raise ValueError(f"shared negatives need a loss.SharedNegativeLoss (softmax_shared, "
+                             f"bpr_shared, top1_shared); the compiled loss is "
+                             f"{type(self.compiled_loss).__name__}")
+        step = self._shared_step
+        self._shared_step += 1
+        neg_ids = self.shared_negative_pool(step)
+        if neg_ids is not None:
+            neg_ids = neg_ids.to(self.compiled_device)
+        q, pos_rows, neg_rows, pos_ids = self._shared_negative_inputs(data, neg_ids)
+        if neg_ids is None:
+            return self.compiled_loss(q, pos_rows, pos_rows, pos_ids, pos_ids)
+        return self.compiled_loss(q, pos_rows, neg_rows, pos_ids, neg_ids.to(pos_ids.dtype))
+
     # -- steps ------------------------------------------------------------------
     def train_step(self, data: Dict):
         self.train()
@@ -463,8 +550,12 @@ class IModel(Module, IWithArguments, ABC):
         data = tensor_to_device(data, self.compiled_device)
         if self._neg_sampler is not None:
             data = self._with_negatives(data)
-        fused = self._fused_loss_fn()
-        if fused is not None:
+        fused = self._fused_loss_fn() if self._shared_source is None else None
+        if self._shared_source is not None:
+            loss = self._shared_negative_loss(data)
+            self.compiled_optimizers.zero_grad()
+            loss.backward()
+        elif fused is not None:
             # output layer + loss (+ their gradients) in one kernel; same math as
             # self(data) followed by compiled_loss (BCEWithLogits, mean)
             loss = fused(data)
@@ -536,9 +627,11 @@ class IModel(Module, IWithArguments, ABC):
         pair_wise = (train_mode is not None
                      and str(getattr(train_mode, "value", train_mode)) == "pair_wise")
         own_negatives = hasattr(dataset, "train_neg_sample")
-        if pair_wise and not own_negatives and self._neg_sampler is None:
+        if (pair_wise and not own_negatives and self._neg_sampler is None
+                and self._shared_source is None):
             raise ValueError("train_mode='pair_wise' needs negatives: a dataset with "
-                             "train_neg_sample(), or model.set_negative_sampler(...)")
+                             "train_neg_sample(), model.set_negative_sampler(...) or "
+                             "model.set_shared_negatives(...)")
         for epoch in range(epochs):
             if pair_wise and own_negatives:  # the dataset's own resampling wins
                 dataset.train_neg_sample()

@@ -173,6 +173,15 @@ class NCF(IModel):
 
     candidate_lists = True  # (recommend_by_forward applies; see the module docstring)
 
+    def set_shared_negatives(self, source, n_shared=None, iid_column=None):
+        """Not available: NCF scores a (user, item) pair with an MLP, not with a dot product
+        of a query vector and an item row, which is what the shared-negative losses take.
+        Train NCF pair-wise (``set_negative_sampler``)."""
+        if source is None:
+            return super().set_shared_negatives(None)
+        raise NotImplementedError("NCF scores pairs with an MLP: there is no query vector to "
+                                  "rank a shared pool of item rows against")
+
     def forward(self, data: Dict[str, Tensor]):
         u_ids = self.uid_column.get_feature_ids(data)
         i_ids = self.iid_column.get_feature_ids(data)

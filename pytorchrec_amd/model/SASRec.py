@@ -192,6 +192,35 @@ class SASRec(IModel):
         """``recommend``: the score is v . i, the query the encoder's output."""
         return self._encode_history(data).float(), self.i_embeddings, 0, False, None
 
+    def _lookup_rows(self, his: Tensor, cand: Tensor) -> Tensor:
+        """History and candidate rows in ONE lookup (one sorted-segment backward, one update
+        per row, as a single nn.Embedding would do): ``[B L + len(cand), D]``, the history
+        first."""
+        bank = self.i_embeddings
+        act_dtype = torch.bfloat16 if bank.weight.is_cuda else torch.float32
+        hist_ids, padded = self._history_lookup_ids(his)
+        cand = cand.to(his.dtype)
+        if padded:
+            past = torch.full_like(his.reshape(-1)[:1], bank.category_nums[0])
+            cand = torch.where(cand < 0, past, cand)
+        return gather(bank, [torch.cat([hist_ids, cand])], out_dtype=act_dtype, pad_negative=padded)
+
+    def _shared_negative_inputs(self, data: Dict[str, Tensor], neg_ids):
+        """History, positives and the pool in the single lookup ``forward`` builds; q is the
+        encoder's output of ``_retrieval_query``, with gradients and dropout."""
+        his = self.his_column.get_feature_ids(data)
+        his_len = self.his_len_column.get_feature_ids(data)
+        if his.dim() != 2:
+            raise ValueError(f"his must be [B, L], got {tuple(his.shape)}")
+        pos_ids = self._shared_positive_ids(data)
+        B, L = his.shape
+        cand = pos_ids if neg_ids is None else torch.cat([pos_ids, neg_ids.to(pos_ids.dtype)])
+        rows = self._lookup_rows(his, cand)
+        v = dense_ops.sasrec_encode(rows[:B * L].reshape(B, L, self.emb_size), his, his_len, self)
+        pos_rows = rows[B * L:B * L + B]
+        neg_rows = rows[B * L + B:] if neg_ids is not None else pos_rows
+        return v.float(), pos_rows, neg_rows, pos_ids
+
     def forward(self, data: Dict[str, Tensor]):
         i_ids = self.iid_column.get_feature_ids(data)
         his = self.his_column.get_feature_ids(data)
@@ -203,16 +232,7 @@ class SASRec(IModel):
             raise ValueError(f"his must be [B, L], got {tuple(his.shape)}")
         B, N = i_ids.shape
         L, D = his.shape[1], self.emb_size
-        bank = self.i_embeddings
-        act_dtype = torch.bfloat16 if bank.weight.is_cuda else torch.float32
-        # history and candidate rows in ONE lookup (one sorted-segment backward, one
-        # update per row, as a single nn.Embedding would do)
-        hist_ids, padded = self._history_lookup_ids(his)
-        cand = i_ids.reshape(-1).to(his.dtype)
-        if padded:
-            past = torch.full_like(his.reshape(-1)[:1], bank.category_nums[0])
-            cand = torch.where(cand < 0, past, cand)
-        rows = gather(bank, [torch.cat([hist_ids, cand])], out_dtype=act_dtype, pad_negative=padded)
+        rows = self._lookup_rows(his, i_ids.reshape(-1))
         v = dense_ops.sasrec_encode(rows[:B * L].reshape(B, L, D), his, his_len, self)
         prediction = (v.unsqueeze(1) * rows[B * L:].reshape(B, N, D).float()).sum(-1)
         target = None

@@ -163,6 +163,15 @@ class SVDPP(IModel):
 
     candidate_lists = True
 
+    def set_shared_negatives(self, source, n_shared=None, iid_column=None):
+        """Not available: SVD++'s score carries a LEARNED item bias, b_i, while the shared-
+        negative losses add only constant biases to ``q . row`` (they get no gradient), so
+        b_i would not train.  Train SVD++ pair-wise (``set_negative_sampler``)."""
+        if source is None:
+            return super().set_shared_negatives(None)
+        raise NotImplementedError("SVDPP scores with a learned item bias, which the shared-"
+                                  "negative losses (constant biases only) cannot train")
+
     def _retrieval_query(self, data: Dict[str, Tensor]):
         """``recommend``: score = (u + imp) . i + b_i, plus b_u + global_bias per sample;
         b_i is the item table's packed first-order column."""
