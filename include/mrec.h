@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MREC_ABI_VERSION 37
+#define MREC_ABI_VERSION 38
 #define MREC_MAX_TABLES 64      /* tables per table bank / per call */
 #define MREC_BWD_MAX_BATCH 8192  /* lookups per table per plan/apply call */
 #define MREC_BWD_HASH_MAX_BATCH 4096  /* batches up to this use the hash plan */
@@ -1903,6 +1903,76 @@ size_t mrec_shneg_workspace_size(int64_t batch, int64_t n_neg, int32_t D, int32_
 mrec_status mrec_shneg_loss_fwd(const mrec_shneg_args *args, mrec_stream stream);
 mrec_status mrec_shneg_loss_bwd(const mrec_shneg_args *args, mrec_stream stream);
 mrec_status mrec_shneg_math_probe(int32_t fn, const float *x, int64_t n, float *y, mrec_stream stream);
+
+/* ------------------------------------------------------------------------- */
+/* DLRM dot interaction: all pairwise dot products of a sample's embedding     */
+/* rows and its bottom-MLP vector, one launch each way (ABI 38;                */
+/* csrc/dot_interact.hip)                                                      */
+/* ------------------------------------------------------------------------- */
+/*
+ * Per sample b, with n = n_fields + 1 vectors of D elements:
+ *   t_0 = bot[b]                       the bottom-MLP output, [batch, D], row stride ld_bot
+ *   t_i = rows[b, (i-1) D : i D]       the gathered rows, [batch, n_fields * D], the layout
+ *                                      mrec_emb_gather_fwd writes, row stride ld_rows
+ *   z[i, j]                = sum_d bf16(t_i[d]) * bf16(t_j[d])     0 <= j < i < n
+ *   x[b, 0 : D]            = t_0                                   (in x's dtype)
+ *   x[b, D + i(i-1)/2 + j] = z[i, j]          P = n (n - 1) / 2 pairs, the order of the
+ *                                             strict lower triangle read row by row
+ *   x[b, D + P : x_cols]   = 0                x_cols >= D + P given by the caller
+ * bf16() is round-to-nearest-even (mrec_topk's operand rounding: exact for bf16 operands);
+ * the products accumulate in fp32 through the MFMA and each z is rounded once, into x's
+ * dtype.  bot may be NULL: there is no bottom vector, n = n_fields, t_i = rows[b, i D :
+ * (i+1) D], x starts with the pairs (x_cols >= P) and dbot is ignored.
+ *   Backward, from dx [batch, >= D + P] (row stride ld_dx), bot and rows again -- nothing
+ * else is kept from the forward:
+ *   G symmetric n x n:  G[i, j] = G[j, i] = dx[b, D + i(i-1)/2 + j]  (i > j),  G[i, i] = 0
+ *   dt_i[d]  = sum_j G[i, j] * bf16(t_j[d])                         fp32 accumulation
+ *   dbot[b]  = dt_0 + dx[b, 0 : D]                                  in bot's dtype
+ *   drows[b, (i-1) D : i D] = dt_i                                  in the rows' dtype
+ * A bf16 dx enters the MFMA exactly; an fp32 dx enters as hi + lo, two bf16 values (hi =
+ * bf16(g), lo = bf16(g - hi), as mrec_shneg_loss_bwd's coefficients: 2^-16 relative).  Each
+ * output is rounded once.
+ *   Determinism.  A sample's outputs are a function of that sample's inputs alone: one wave
+ * per sample, no atomics, no sum across waves, so the bits do not depend on the batch, the
+ * grid, the sample's position or the run.
+ *   One description for both directions: the forward ignores dx, dbot and drows; the
+ * backward ignores x and x_cols.
+ * Compiled shapes (mrec_dot_interact_supported): D in {8, 16, 32, 64, 128}, 1 <= n_fields
+ * <= 31, bot, rows, x and dx each MREC_F32 or MREC_BF16, independently; any batch up to
+ * 2^31 - 1 (batch = 0 launches nothing).  Every operand and output needs 16-byte aligned
+ * rows (pointer and row stride in bytes multiples of 16) of at least its width.  Never read:
+ * columns >= D of a bot row, >= n_fields * D of a rows row, >= D + P of a dx row; never
+ * written: columns >= x_cols of x, >= D of dbot, >= n_fields * D of drows, and rows >= batch.
+ * Caller-owned buffers, no allocation, no host synchronisation, all work on `stream`;
+ * anything else is MREC_EINVAL with mrec_last_error() before any launch.
+ */
+typedef struct {
+  const void *bot;
+  mrec_dtype bot_dtype;
+  int64_t ld_bot;
+  const void *rows;
+  mrec_dtype rows_dtype;
+  int64_t ld_rows;
+  int64_t batch;
+  int32_t n_fields;
+  int32_t D;
+  void *x;
+  mrec_dtype x_dtype;
+  int64_t ld_x;
+  int64_t x_cols;
+  const void *dx;
+  mrec_dtype dx_dtype;
+  int64_t ld_dx;
+  void *dbot;
+  int64_t ld_dbot;
+  void *drows;
+  int64_t ld_drows;
+} mrec_dot_interact_args;
+
+int32_t mrec_dot_interact_supported(int32_t D, int32_t n_fields, mrec_dtype bot_dtype,
+                                    mrec_dtype rows_dtype, mrec_dtype x_dtype, mrec_dtype dx_dtype);
+mrec_status mrec_dot_interact_fwd(const mrec_dot_interact_args *args, mrec_stream stream);
+mrec_status mrec_dot_interact_bwd(const mrec_dot_interact_args *args, mrec_stream stream);
 
 #ifdef __cplusplus
 }

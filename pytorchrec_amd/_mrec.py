@@ -20,7 +20,7 @@ import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("MREC_LIB_PATH") or os.path.join(LIB_DIR, "libmrec.so")
 
-ABI_VERSION = 37
+ABI_VERSION = 38
 MAX_TABLES = 64
 BWD_MAX_BATCH = 8192
 BWD_HASH_MAX_BATCH = 4096  # batches up to this use the hash plan (fusable into a GEMM launch)
@@ -309,6 +309,18 @@ class ShnegArgs(ctypes.Structure):
                 ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
 
 
+class DotInteractArgs(ctypes.Structure):
+    """mrec_dot_interact_args (include/mrec.h, ABI 38): one description for both directions."""
+    _fields_ = [("bot", ctypes.c_void_p), ("bot_dtype", ctypes.c_int), ("ld_bot", ctypes.c_int64),
+                ("rows", ctypes.c_void_p), ("rows_dtype", ctypes.c_int), ("ld_rows", ctypes.c_int64),
+                ("batch", ctypes.c_int64), ("n_fields", ctypes.c_int32), ("D", ctypes.c_int32),
+                ("x", ctypes.c_void_p), ("x_dtype", ctypes.c_int), ("ld_x", ctypes.c_int64),
+                ("x_cols", ctypes.c_int64),
+                ("dx", ctypes.c_void_p), ("dx_dtype", ctypes.c_int), ("ld_dx", ctypes.c_int64),
+                ("dbot", ctypes.c_void_p), ("ld_dbot", ctypes.c_int64),
+                ("drows", ctypes.c_void_p), ("ld_drows", ctypes.c_int64)]
+
+
 LAYOUT_ROW, LAYOUT_COL = 0, 1
 ACT_NONE, ACT_RELU = 0, 1
 
@@ -520,6 +532,10 @@ SIGNATURES = {
     "mrec_shneg_loss_fwd": (ctypes.c_int, [ctypes.POINTER(ShnegArgs), _vp]),
     "mrec_shneg_loss_bwd": (ctypes.c_int, [ctypes.POINTER(ShnegArgs), _vp]),
     "mrec_shneg_math_probe": (ctypes.c_int, [_i32, _vp, _i64, _vp, _vp]),
+    "mrec_dot_interact_supported": (ctypes.c_int32, [_i32, _i32, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                     ctypes.c_int]),
+    "mrec_dot_interact_fwd": (ctypes.c_int, [ctypes.POINTER(DotInteractArgs), _vp]),
+    "mrec_dot_interact_bwd": (ctypes.c_int, [ctypes.POINTER(DotInteractArgs), _vp]),
     "mrec_tower_fwd_bwd": (ctypes.c_int, [ctypes.POINTER(TowerArgs), _vp]),
     "mrec_tower_image_elems": (ctypes.c_int64, [_i64, _i64, _i32]),
     "mrec_tower_weight_prep": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),

@@ -13,7 +13,9 @@ the layered path for the shapes and modes the fused kernels do not cover
 (``dense.gru_encode`` decides).  ``topk`` is ``mrec_topk``, the full-catalogue retrieval, in
 torch ops, chunked over the items (``retrieval.topk`` decides).  ``shared_negative_loss`` is
 ``mrec_shneg_loss_fwd`` / ``_bwd``, the list-wise losses over a shared pool of negatives, in
-differentiable torch ops (``loss.SharedNegativeLoss`` decides).
+differentiable torch ops (``loss.SharedNegativeLoss`` decides).  ``dot_interact`` is
+``mrec_dot_interact_fwd`` / ``_bwd``, DLRM's pairwise dot interaction, in the same way
+(``dense.dot_interact`` decides).
 """
 from __future__ import annotations
 
@@ -473,3 +475,37 @@ def shared_negative_loss(q, pos, neg, kind: str, reduction: str = "mean", pos_id
     if reduction == "none":
         return loss
     return loss.sum() / max(B, 1) if reduction == "mean" else loss.sum()
+
+
+def dot_interact(bot, rows, F: int, D: int, x_cols: Optional[int] = None, round_bf16: bool = False,
+                 x_dtype=None):
+    """``mrec_dot_interact_fwd`` / ``_bwd`` in differentiable torch ops (include/mrec.h "DLRM
+    dot interaction"): per sample the n = F + 1 vectors t_0 = ``bot [B, D]``, t_i = field i - 1
+    of ``rows [B, F * D]`` (``bot`` None: the F rows alone) ->
+    ``x [B, x_cols] = [t_0 | t_i . t_j for 0 <= j < i < n | 0 pad]``, the pairs in the order of
+    ``torch.tril_indices(n, n, -1)``; ``x_cols`` None is D + P exactly.  Arithmetic in fp32
+    (fp64 operands stay fp64), which is what the model's CPU forward computes; ``round_bf16``
+    rounds the operands of the products to bf16 first (identity gradient), the kernel's operand
+    rounding: the GPU path of a shape the kernel does not cover, and its comparator.  The copy
+    of t_0 is never rounded.  Autograd is the backward: G symmetric with a zero diagonal times
+    the (rounded) vectors, plus dx[:, :D] for ``bot``.  -> x in ``x_dtype`` (None: the
+    arithmetic's)."""
+    dt = torch.float64 if rows.dtype == torch.float64 else torch.float32
+    B = rows.shape[0]
+    t = rows[:, :F * D].to(dt).reshape(B, F, D)
+    head = []
+    if bot is not None:
+        b0 = bot[:, :D].to(dt)
+        head = [b0]
+        t = torch.cat([b0.unsqueeze(1), t], dim=1)
+    n = t.shape[1]
+    tb = bf16_round(t) if round_bf16 else t
+    z = torch.bmm(tb, tb.transpose(1, 2))
+    li, lj = torch.tril_indices(n, n, -1, device=rows.device)
+    x = torch.cat(head + [z[:, li, lj]], dim=1)
+    if x_cols is not None:
+        if x_cols < x.shape[1]:
+            raise ValueError(f"x_cols = {x_cols} is smaller than D + P = {x.shape[1]}")
+        if x_cols > x.shape[1]:
+            x = torch.nn.functional.pad(x, (0, x_cols - x.shape[1]))
+    return x if x_dtype is None else x.to(x_dtype)

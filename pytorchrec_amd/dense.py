@@ -1,5 +1,5 @@
 """Dense-tower ops: Linear(+bias)(+ReLU), DCN-v2 cross, DIN attention pooling, the
-SASRec encoder.
+SASRec / GRU4Rec encoders, the NCF scorer, DLRM's pairwise dot interaction.
 
 One seam for the model code.  On a GPU they run on libmrec's MFMA bf16 GEMM
 (``mrec_gemm``: fp32 accumulation, bias / ReLU / DCN epilogues fused, the fp32
@@ -1273,6 +1273,112 @@ def ncf_score(rows: torch.Tensor, model) -> torch.Tensor:
     return cpu_path.ncf_score(rows, E, ws, bs, wp,
                               rnd=cpu_path.bf16_round if rows.is_cuda else None,
                               dropout=drop, training=model.training)
+
+
+# the fused DLRM dot interaction (mrec_dot_interact_*, dot_interact.hip) is the default for
+# the compiled shapes; False selects the torch-ops path (the parity tests and the benchmark
+# set it)
+DOT_INTERACT = True
+
+_DI_DTYPES = (torch.float32, _BF16)
+
+
+def dot_interact_supported(D: int, n_fields: int, bot_dtype=torch.float32,
+                           rows_dtype=torch.float32, x_dtype=torch.float32,
+                           dx_dtype=torch.float32) -> bool:
+    """True when the fused interaction covers (D, n_fields) and the four dtypes.  Decided
+    from the shape alone; never an error."""
+    dts = (bot_dtype, rows_dtype, x_dtype, dx_dtype)
+    if any(t not in _DI_DTYPES for t in dts):
+        return False
+    return bool(_mrec.lib().mrec_dot_interact_supported(int(D), int(n_fields),
+                                                        *[_mrec.dtype_code(t) for t in dts]))
+
+
+def _rows16(t: torch.Tensor) -> torch.Tensor:
+    """[M, N] with unit inner stride and 16-byte aligned rows; copies only when it must."""
+    es = t.element_size()
+    if (t.stride(1) == 1 and t.stride(0) >= t.shape[1] and (t.stride(0) * es) % 16 == 0
+            and t.data_ptr() % 16 == 0):
+        return t
+    out = _alloc(t.shape[0], t.shape[1], t.dtype, t.device)
+    out.copy_(t)
+    return out
+
+
+class _DotInteractFn(torch.autograd.Function):
+    """x = [bot | pairwise dots | 0 pad] of the gathered rows and the bottom vector: one
+    forward launch, one backward launch (dbot in bot's dtype, drows in the rows'), nothing
+    saved but the two inputs."""
+
+    @staticmethod
+    def forward(ctx, bot, rows, F_: int, D: int, x_cols: int, x_dtype):
+        B, dev = rows.shape[0], rows.device
+        rows2 = _rows16(rows.detach())
+        bot2 = _rows16(bot.detach()) if bot is not None else None
+        x = _alloc(B, x_cols, x_dtype, dev)
+        a = _mrec.DotInteractArgs()
+        if bot2 is not None:
+            a.bot, a.bot_dtype, a.ld_bot = bot2.data_ptr(), _mrec.dtype_code(bot2.dtype), bot2.stride(0)
+        a.rows, a.rows_dtype, a.ld_rows = rows2.data_ptr(), _mrec.dtype_code(rows2.dtype), rows2.stride(0)
+        a.batch, a.n_fields, a.D = B, int(F_), int(D)
+        a.x, a.x_dtype, a.ld_x, a.x_cols = x.data_ptr(), _mrec.dtype_code(x_dtype), x.stride(0), int(x_cols)
+        if B:
+            _mrec.call("mrec_dot_interact_fwd", ctypes.byref(a), _mrec.stream_handle())
+        ctx.args, ctx.keep = a, (bot2, rows2)
+        return x
+
+    @staticmethod
+    def backward(ctx, dx):
+        a, (bot2, rows2) = ctx.args, ctx.keep
+        B, F_, D = int(a.batch), int(a.n_fields), int(a.D)
+        dev = rows2.device
+        dx = dx.detach()
+        if dx.dtype not in _DI_DTYPES:
+            dx = dx.float()
+        dx = _rows16(dx)
+        dbot = _alloc(B, D, bot2.dtype, dev) if bot2 is not None else None
+        drows = _alloc(B, F_ * D, rows2.dtype, dev)
+        a.dx, a.dx_dtype, a.ld_dx = dx.data_ptr(), _mrec.dtype_code(dx.dtype), dx.stride(0)
+        if dbot is not None:
+            a.dbot, a.ld_dbot = dbot.data_ptr(), dbot.stride(0)
+        a.drows, a.ld_drows = drows.data_ptr(), drows.stride(0)
+        if B:
+            _mrec.call("mrec_dot_interact_bwd", ctypes.byref(a), _mrec.stream_handle())
+        ctx.args = ctx.keep = None
+        return dbot, drows, None, None, None, None
+
+
+def dot_interact(bot: Optional[torch.Tensor], rows: torch.Tensor, n_fields: int,
+                 x_cols: Optional[int] = None, x_dtype=None) -> torch.Tensor:
+    """DLRM's pairwise dot interaction (include/mrec.h "DLRM dot interaction"): with t_0 =
+    ``bot [B, D]`` (None: no bottom vector) and t_i the fields of ``rows [B, n_fields * D]``
+    (``embedding.gather``'s layout), x ``[B, x_cols] = [t_0 | t_i . t_j, j < i | 0 pad]`` in
+    ``x_dtype`` (default: the rows'), the pairs in ``torch.tril_indices`` order.  ``x_cols``
+    defaults to D + P rounded up to 8, the row pitch ``tower_supported`` asks of x0.  On a GPU
+    the fused kernels for the compiled shapes; else, and on the CPU, the same contract as
+    torch ops (``cpu_path.dot_interact``), rounding the operands to bf16 on a GPU where the
+    kernel does."""
+    from pytorchrec_amd import cpu_path
+    F_ = int(n_fields)
+    if F_ < 1 or rows.dim() != 2 or rows.shape[1] % F_:
+        raise ValueError(f"rows must be [B, n_fields * D], got {tuple(rows.shape)} for {F_} fields")
+    D = rows.shape[1] // F_
+    if bot is not None and (bot.dim() != 2 or bot.shape[0] != rows.shape[0] or bot.shape[1] != D):
+        raise ValueError(f"bot must be [B, {D}], got {tuple(bot.shape)}")
+    n = F_ + (bot is not None)
+    width = (D if bot is not None else 0) + n * (n - 1) // 2
+    if x_cols is None:
+        x_cols = _r8(width)
+    if x_cols < width:
+        raise ValueError(f"x_cols = {x_cols} is smaller than D + P = {width}")
+    x_dtype = x_dtype or rows.dtype
+    if (rows.is_cuda and DOT_INTERACT
+            and dot_interact_supported(D, F_, bot.dtype if bot is not None else torch.float32,
+                                       rows.dtype, x_dtype)):
+        return _DotInteractFn.apply(bot, rows, F_, D, int(x_cols), x_dtype)
+    return cpu_path.dot_interact(bot, rows, F_, D, int(x_cols), round_bf16=rows.is_cuda,
+                                 x_dtype=x_dtype)
 
 
 def colsum(s: torch.Tensor, X: Optional[torch.Tensor], want_total: bool = True, *,

@@ -4,6 +4,7 @@ from typing import Dict, Type
 from pytorchrec_amd.model.DCNv2 import DCNv2
 from pytorchrec_amd.model.DeepFM import FM, DeepFM
 from pytorchrec_amd.model.DIN import DIN
+from pytorchrec_amd.model.DLRM import DLRM
 from pytorchrec_amd.model.FunkSVD import FunkSVD
 from pytorchrec_amd.model.GRU4Rec import GRU4Rec
 from pytorchrec_amd.model.IModel import IModel
@@ -21,6 +22,7 @@ _model_classes: Dict[str, Type[IModel]] = {
     "deepfm": DeepFM,
     "dcnv2": DCNv2,
     "din": DIN,
+    "dlrm": DLRM,
 }
 
 model_name_list = _model_classes.keys()
