@@ -26,6 +26,9 @@ void set_error(const std::string &msg);
 
 mrec_status launch_status(const char *what);  // hipGetLastError -> status
 
+// compute units of the device current at the first call (cached; 256 if the query fails)
+int device_cus();
+
 // ---------------------------------------------------------------------------
 // Embedding-backward workspace layout tags (ABI 28).  A plan decides the layout
 // (sorted or hash) from its batch and whether its ids are a padded exchange view;

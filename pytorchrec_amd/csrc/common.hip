@@ -19,6 +19,18 @@ mrec_status launch_status(const char *what) {
   return MREC_OK;
 }
 
+int device_cus() {
+  static const int n = [] {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
+      v = 256;
+    (void)hipGetLastError();
+    return v;
+  }();
+  return n;
+}
+
 // workspace layout records (common.h): address -> the last plan issued into it
 namespace {
 struct WsRecord {

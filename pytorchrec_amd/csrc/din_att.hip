@@ -28,11 +28,9 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "frag.h"
 
 namespace mrec {
-
-typedef short da_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float da_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int DA_ROWS = 64;              // history positions per sample, padded
 constexpr int DA_CG = 2;                 // column groups: 8 waves = 4 row tiles x 2
@@ -67,14 +65,10 @@ struct DinAttArgs {
       p.stamps[(k)] = __builtin_amdgcn_s_memtime();                   \
   } while (0)
 
-__device__ __forceinline__ da_bf16x8 da_frag(const uint16_t *base, int ld, int r0, int k0,
-                                             int lane) {
-  return *reinterpret_cast<const da_bf16x8 *>(base + (r0 + (lane & 15)) * ld + k0 +
+__device__ __forceinline__ bf16x8 da_frag(const uint16_t *base, int ld, int r0, int k0,
+                                          int lane) {
+  return *reinterpret_cast<const bf16x8 *>(base + (r0 + (lane & 15)) * ld + k0 +
                                               8 * (lane >> 4));
-}
-
-__device__ __forceinline__ da_f32x4 da_mfma(da_bf16x8 a, da_bf16x8 b, da_f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
 // sum over the 16 lanes of a row group (lanes 16 g .. 16 g + 15)
@@ -245,18 +239,18 @@ __device__ __forceinline__ void da_build_x(const DinAttArgs &p, const DaRaw &raw
 // layer 1: acc[jn] = X[rows] W1^T (tile n = cg + DA_CG jn)
 template <class S, int H1T>
 __device__ __forceinline__ void da_layer1(const uint16_t *sm, int rt, int cg, int lane, bool on,
-                                          da_f32x4 (&acc)[(H1T + DA_CG - 1) / DA_CG]) {
+                                          f32x4 (&acc)[(H1T + DA_CG - 1) / DA_CG]) {
   constexpr int J = (H1T + DA_CG - 1) / DA_CG;
 #pragma unroll
-  for (int jn = 0; jn < J; ++jn) acc[jn] = da_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int jn = 0; jn < J; ++jn) acc[jn] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (!on) return;
 #pragma unroll
   for (int s = 0; s < S::KT1; ++s) {
-    const da_bf16x8 a = da_frag(sm + S::oX, S::LDX, 16 * rt, 32 * s, lane);
+    const bf16x8 a = da_frag(sm + S::oX, S::LDX, 16 * rt, 32 * s, lane);
 #pragma unroll
     for (int jn = 0; jn < J; ++jn) {
       const int n = cg + DA_CG * jn;
-      if (n < H1T) acc[jn] = da_mfma(a, da_frag(sm + S::oW1, S::LDX, 16 * n, 32 * s, lane), acc[jn]);
+      if (n < H1T) acc[jn] = mfma_16x16x32(a, da_frag(sm + S::oW1, S::LDX, 16 * n, 32 * s, lane), acc[jn]);
     }
   }
 }
@@ -264,18 +258,18 @@ __device__ __forceinline__ void da_layer1(const uint16_t *sm, int rt, int cg, in
 // layer 2: acc[jn] = H1[rows] W2^T
 template <class S, int H1K, int H2T>
 __device__ __forceinline__ void da_layer2(const uint16_t *sm, int rt, int cg, int lane, bool on,
-                                          da_f32x4 (&acc)[(H2T + DA_CG - 1) / DA_CG]) {
+                                          f32x4 (&acc)[(H2T + DA_CG - 1) / DA_CG]) {
   constexpr int J = (H2T + DA_CG - 1) / DA_CG;
 #pragma unroll
-  for (int jn = 0; jn < J; ++jn) acc[jn] = da_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int jn = 0; jn < J; ++jn) acc[jn] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (!on) return;
 #pragma unroll
   for (int s = 0; s < H1K; ++s) {
-    const da_bf16x8 a = da_frag(sm + S::oH1, S::LDH, 16 * rt, 32 * s, lane);
+    const bf16x8 a = da_frag(sm + S::oH1, S::LDH, 16 * rt, 32 * s, lane);
 #pragma unroll
     for (int jn = 0; jn < J; ++jn) {
       const int n = cg + DA_CG * jn;
-      if (n < H2T) acc[jn] = da_mfma(a, da_frag(sm + S::oW2, S::LDH, 16 * n, 32 * s, lane), acc[jn]);
+      if (n < H2T) acc[jn] = mfma_16x16x32(a, da_frag(sm + S::oW2, S::LDH, 16 * n, 32 * s, lane), acc[jn]);
     }
   }
 }
@@ -318,7 +312,7 @@ __global__ __launch_bounds__(DA_THREADS) void din_att_fwd_kernel(DinAttArgs p) {
     if (b + gridDim.x < p.batch) nxt = da_load<E, false>(p, b + gridDim.x, task, lane);
     __syncthreads();
     {
-      da_f32x4 acc[J1];
+      f32x4 acc[J1];
       da_layer1<S, H1T>(sm, rt, cg, lane, act, acc);
 #pragma unroll
       for (int jn = 0; jn < J1; ++jn) {
@@ -335,7 +329,7 @@ __global__ __launch_bounds__(DA_THREADS) void din_att_fwd_kernel(DinAttArgs p) {
     }
     __syncthreads();
     {
-      da_f32x4 acc[J2];
+      f32x4 acc[J2];
       da_layer2<S, H1K, H2T>(sm, rt, cg, lane, act, acc);
       float part[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -502,7 +496,7 @@ __global__ __launch_bounds__(DA_THREADS, 1) void din_att_fwd_wave_kernel(DinAttA
   DA_STAMP(1);
   // layer 1's B fragments in VGPRs (80 at C4); layer 2's are read from the staged
   // copy per use (in VGPRs too they spill at 256)
-  da_bf16x8 w1f[H1T][KT1];
+  bf16x8 w1f[H1T][KT1];
   float b1v[H1T][4], b2v[H2T], w3v[H2T];
 #pragma unroll
   for (int n = 0; n < H1T; ++n) {
@@ -547,16 +541,16 @@ __global__ __launch_bounds__(DA_THREADS, 1) void din_att_fwd_wave_kernel(DinAttA
                         pack_bf16x2(m[4], m[5]), pack_bf16x2(m[6], m[7]));
       }
       if (!real) qq = dq = mq = make_uint4(0, 0, 0, 0);
-      da_f32x4 acc[H1T];
+      f32x4 acc[H1T];
 #pragma unroll
-      for (int n = 0; n < H1T; ++n) acc[n] = da_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int n = 0; n < H1T; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int s = 0; s < KT1; ++s) {
         const int blk = (32 * s + 8 * g) / E;
         const uint4 xv = blk == 0 ? qq : blk == 1 ? kk : blk == 2 ? dq : mq;
-        const da_bf16x8 a = __builtin_bit_cast(da_bf16x8, xv);
+        const bf16x8 a = __builtin_bit_cast(bf16x8, xv);
 #pragma unroll
-        for (int n = 0; n < H1T; ++n) acc[n] = da_mfma(w1f[n][s], a, acc[n]);
+        for (int n = 0; n < H1T; ++n) acc[n] = mfma_16x16x32(w1f[n][s], a, acc[n]);
       }
       // (operands swapped: acc[n] is H1^T, lane l holds row l % 16's outputs
       // 16 n + 4 (l / 16) .. + 3 -- the same products and k order, one 8-B store each)
@@ -570,15 +564,15 @@ __global__ __launch_bounds__(DA_THREADS, 1) void din_att_fwd_wave_kernel(DinAttA
             make_uint2(pack_bf16x2(h[0], h[1]), pack_bf16x2(h[2], h[3]));
       }
       DA_WAVE_SYNC();
-      da_f32x4 acc2[H2T];
+      f32x4 acc2[H2T];
 #pragma unroll
-      for (int n = 0; n < H2T; ++n) acc2[n] = da_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int n = 0; n < H2T; ++n) acc2[n] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int s = 0; s < H1K; ++s) {
-        const da_bf16x8 a = da_frag(sHt, LDH, 0, 32 * s, lane);
+        const bf16x8 a = da_frag(sHt, LDH, 0, 32 * s, lane);
 #pragma unroll
         for (int n = 0; n < H2T; ++n)
-          acc2[n] = da_mfma(a, da_frag(sm + S::oW2, LDH, 16 * n, 32 * s, lane), acc2[n]);
+          acc2[n] = mfma_16x16x32(a, da_frag(sm + S::oW2, LDH, 16 * n, 32 * s, lane), acc2[n]);
       }
       float part[DA_CG][4] = {};
 #pragma unroll
@@ -696,17 +690,12 @@ struct DaShape2 : DaShape<E, H1T, H1K, H2T, H2K> {
 };
 
 // MFMA operand fragment with k running down the rows of a row-major bf16 buffer:
-// lane l gets column c0 + l % 16, rows r0 + 8 (l / 16) .. + 8 (two
-// ds_read_b64_tr_b16: each 16-lane group addresses 4 rows x 4 column quads)
-__device__ __forceinline__ da_bf16x8 da_frag_tr(const uint16_t *base, int ld, int c0, int r0,
-                                                int lane) {
-  typedef short v4s_t __attribute__((ext_vector_type(4)));
-  typedef __attribute__((address_space(3))) v4s_t lds_v4s_t;
+// lane l gets column c0 + l % 16, rows r0 + 8 (l / 16) .. + 8 (two transposing reads,
+// frag.h: each 16-lane group addresses 4 rows x 4 column quads)
+__device__ __forceinline__ bf16x8 da_frag_tr(const uint16_t *base, int ld, int c0, int r0, int lane) {
   const int i = lane & 15, g = lane >> 4;
   const uint16_t *q = base + (r0 + 8 * g + (i >> 2)) * ld + c0 + 4 * (i & 3);
-  const v4s_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t *)(q));
-  const v4s_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t *)(q + 4 * ld));
-  return da_bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return lds_tr16_pair(q, 4 * ld);
 }
 
 // X rows of one sample, row-major only: [q | k | q - k | q * k] (rows >= L zero)
@@ -771,11 +760,11 @@ __global__ __launch_bounds__(DA_THREADS) void din_att_bwd2_kernel(DinAttArgs p, 
   int sidx = 0;
   DA_STAMP(1);
 
-  da_f32x4 gw1[NW1], gw2[NW2];
+  f32x4 gw1[NW1], gw2[NW2];
 #pragma unroll
-  for (int i = 0; i < NW1; ++i) gw1[i] = da_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int i = 0; i < NW1; ++i) gw1[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int i = 0; i < NW2; ++i) gw2[i] = da_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int i = 0; i < NW2; ++i) gw2[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   float gb1[H1T], gb2[H2T], gw3[H2T];  // per-lane column partials (column 16 n + lane % 16)
 #pragma unroll
   for (int n = 0; n < H1T; ++n) gb1[n] = 0.f;
@@ -845,15 +834,15 @@ __global__ __launch_bounds__(DA_THREADS) void din_att_bwd2_kernel(DinAttArgs p, 
     const float dsj = aj * (gj - ag);
     if (rt == 0) gb3 += sum_wave(dsj);
     {
-      da_f32x4 acc[H1T];
+      f32x4 acc[H1T];
 #pragma unroll
-      for (int n = 0; n < H1T; ++n) acc[n] = da_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int n = 0; n < H1T; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (act) {
 #pragma unroll
         for (int s = 0; s < S::KT1; ++s) {
-          const da_bf16x8 a = da_frag(X, LDX, 16 * rt, 32 * s, lane);
+          const bf16x8 a = da_frag(X, LDX, 16 * rt, 32 * s, lane);
 #pragma unroll
-          for (int n = 0; n < H1T; ++n) acc[n] = da_mfma(a, da_frag(W1, LDX, 16 * n, 32 * s, lane), acc[n]);
+          for (int n = 0; n < H1T; ++n) acc[n] = mfma_16x16x32(a, da_frag(W1, LDX, 16 * n, 32 * s, lane), acc[n]);
         }
       }
 #pragma unroll
@@ -869,15 +858,15 @@ __global__ __launch_bounds__(DA_THREADS) void din_att_bwd2_kernel(DinAttArgs p, 
     }
     // ---- layer 2, dZ2 = ds w3 relu'(z2) -> dZ2 (own rows) ----
     {
-      da_f32x4 acc[H2T];
+      f32x4 acc[H2T];
 #pragma unroll
-      for (int n = 0; n < H2T; ++n) acc[n] = da_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int n = 0; n < H2T; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (act) {
 #pragma unroll
         for (int s = 0; s < H1K; ++s) {
-          const da_bf16x8 a = da_frag(Hb, LDH, 16 * rt, 32 * s, lane);
+          const bf16x8 a = da_frag(Hb, LDH, 16 * rt, 32 * s, lane);
 #pragma unroll
-          for (int n = 0; n < H2T; ++n) acc[n] = da_mfma(a, da_frag(W2, LDH, 16 * n, 32 * s, lane), acc[n]);
+          for (int n = 0; n < H2T; ++n) acc[n] = mfma_16x16x32(a, da_frag(W2, LDH, 16 * n, 32 * s, lane), acc[n]);
         }
       }
 #pragma unroll
@@ -898,16 +887,16 @@ __global__ __launch_bounds__(DA_THREADS) void din_att_bwd2_kernel(DinAttArgs p, 
     }
     // ---- dH1 = dZ2 W2, dZ1 = dH1 relu'(H1) -> dZ1 (own rows) ----
     {
-      da_f32x4 acc[H1T];
+      f32x4 acc[H1T];
 #pragma unroll
-      for (int n = 0; n < H1T; ++n) acc[n] = da_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int n = 0; n < H1T; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (act) {
 #pragma unroll
         for (int s = 0; s < H2K; ++s) {
-          const da_bf16x8 a = da_frag(Z2, LDZ2, 16 * rt, 32 * s, lane);
+          const bf16x8 a = da_frag(Z2, LDZ2, 16 * rt, 32 * s, lane);
 #pragma unroll
           for (int n = 0; n < H1T; ++n)
-            acc[n] = da_mfma(a, da_frag_tr(W2, LDH, 16 * n, 32 * s, lane), acc[n]);
+            acc[n] = mfma_16x16x32(a, da_frag_tr(W2, LDH, 16 * n, 32 * s, lane), acc[n]);
         }
       }
 #pragma unroll
@@ -938,8 +927,8 @@ __global__ __launch_bounds__(DA_THREADS) void din_att_bwd2_kernel(DinAttArgs p, 
           const int t = w + NWV * i;
           if (t < H2T * H1T) {
             const int m = t / H1T, n = t - m * H1T;
-            gw2[i] = da_mfma(da_frag_tr(z2, LDZ2, 16 * m, 32 * s, lane),
-                             da_frag_tr(h1, LDH, 16 * n, 32 * s, lane), gw2[i]);
+            gw2[i] = mfma_16x16x32(da_frag_tr(z2, LDZ2, 16 * m, 32 * s, lane),
+                                   da_frag_tr(h1, LDH, 16 * n, 32 * s, lane), gw2[i]);
           }
         }
       }
@@ -948,16 +937,16 @@ __global__ __launch_bounds__(DA_THREADS) void din_att_bwd2_kernel(DinAttArgs p, 
     // q / k / q-k / q*k at a time (registers) ----
 #pragma unroll 1
     for (int c16 = 0; c16 < EC; ++c16) {
-      da_f32x4 acc[4];
+      f32x4 acc[4];
 #pragma unroll
-      for (int blk = 0; blk < 4; ++blk) acc[blk] = da_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int blk = 0; blk < 4; ++blk) acc[blk] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (act) {
 #pragma unroll
         for (int s = 0; s < H1K; ++s) {
-          const da_bf16x8 a = da_frag(Z1, LDH, 16 * rt, 32 * s, lane);
+          const bf16x8 a = da_frag(Z1, LDH, 16 * rt, 32 * s, lane);
 #pragma unroll
           for (int blk = 0; blk < 4; ++blk)
-            acc[blk] = da_mfma(a, da_frag_tr(W1, LDX, 16 * (blk * EC + c16), 32 * s, lane), acc[blk]);
+            acc[blk] = mfma_16x16x32(a, da_frag_tr(W1, LDX, 16 * (blk * EC + c16), 32 * s, lane), acc[blk]);
         }
       }
       const int e = 16 * c16 + (lane & 15);
@@ -1004,8 +993,8 @@ __global__ __launch_bounds__(DA_THREADS) void din_att_bwd2_kernel(DinAttArgs p, 
           const int t = w + NWV * i;
           if (t < H1T * NTX) {
             const int m = t / NTX, n = t - m * NTX;
-            gw1[i] = da_mfma(da_frag_tr(z1, LDH, 16 * m, 32 * s, lane),
-                             da_frag_tr(x, LDX, 16 * n, 32 * s, lane), gw1[i]);
+            gw1[i] = mfma_16x16x32(da_frag_tr(z1, LDH, 16 * m, 32 * s, lane),
+                                   da_frag_tr(x, LDX, 16 * n, 32 * s, lane), gw1[i]);
           }
         }
       }
@@ -1169,19 +1158,6 @@ bool da_match(int e, int h1, int h2) {
          (h2 + 31) / 32 == H2K;
 }
 
-int da_cus() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        v <= 0)
-      v = 256;
-    (void)hipGetLastError();
-    return v;
-  }();
-  return n;
-}
-
 template <int E, int H1T, int H1K, int H2T, int H2K>
 void da_set_attrs() {
   using S = DaShape<E, H1T, H1K, H2T, H2K>;
@@ -1233,7 +1209,7 @@ int32_t mrec_din_att_supported(int32_t E, int32_t H1, int32_t H2) {
 }
 
 int64_t mrec_din_att_parts(int64_t batch) {
-  const int64_t g = da_cus();
+  const int64_t g = device_cus();
   return batch < g ? (batch > 0 ? batch : 1) : g;
 }
 
@@ -1283,8 +1259,8 @@ mrec_status mrec_din_att_fwd(const void *rows, int64_t ld_rows, const int32_t *h
   p.stamps = g_da_stamps_fwd ? g_da_stamps : nullptr;
   const bool wg = da_fwd_wg();
   // one workgroup (8 sample waves) per CU, or one sample per workgroup
-  const int64_t grid = wg ? std::min<int64_t>(batch, 2 * static_cast<int64_t>(da_cus()))
-                          : std::min<int64_t>((batch + 7) / 8, da_cus());
+  const int64_t grid = wg ? std::min<int64_t>(batch, 2 * static_cast<int64_t>(device_cus()))
+                          : std::min<int64_t>((batch + 7) / 8, device_cus());
   hipStream_t s = static_cast<hipStream_t>(stream);
 #define X(e, h1t, h1k, h2t, h2k)                                                              \
   if (da_match<e, h1t, h1k, h2t, h2k>(E, H1, H2)) {                                         \

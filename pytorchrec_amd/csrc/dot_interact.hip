@@ -26,11 +26,9 @@
 // Nothing is summed across waves and there are no atomics: a sample's bits depend on that
 // sample's inputs alone.
 #include "common.h"
+#include "frag.h"
 
 namespace mrec {
-
-typedef short di_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float di_f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int DI_W = 4;                 // waves (samples) per workgroup
 constexpr int DI_THREADS = 64 * DI_W;
@@ -38,73 +36,29 @@ constexpr int DI_MAXP = 32 * 31 / 2;    // pairs of a full tile
 constexpr int DI_IMG = 128 + DI_MAXP;   // fp32 image of [t_0 | pairs]
 constexpr int DI_TLD = 40;              // row pitch of the transposed T image (bf16 elements)
 
-struct DiMat {
-  const char *p;
-  int64_t ld_bytes;
-  int32_t bf16;
-};
-
-struct DiOut {
-  char *p;
-  int64_t ld_bytes;
-  int32_t bf16;
-};
-
 struct DiArgs {
-  DiMat bot, rows, dx;
-  DiOut x, dbot, drows;
+  MatIn bot, rows, dx;
+  MatOut x, dbot, drows;
   int64_t B, x_cols;
   int32_t n;        // vectors per sample (fields + the bottom vector)
   int32_t has_bot;  // vector 0 is bot[b]; else every vector is a row
 };
 
-__device__ __forceinline__ di_bf16x8 di_zero8() {
-  return __builtin_bit_cast(di_bf16x8, make_uint4(0, 0, 0, 0));
-}
-
-// elements [col0, col0 + 8) of a row as one MFMA fragment (an fp32 row is rounded here)
-__device__ __forceinline__ di_bf16x8 di_load8(const DiMat &m, int64_t row, int col0) {
-  const char *rp = m.p + row * m.ld_bytes;
-  if (m.bf16) return __builtin_bit_cast(di_bf16x8, *reinterpret_cast<const uint4 *>(rp + 2 * col0));
-  const uint4 a = *reinterpret_cast<const uint4 *>(rp + 4 * col0);
-  const uint4 b = *reinterpret_cast<const uint4 *>(rp + 4 * col0 + 16);
-  return __builtin_bit_cast(
-      di_bf16x8, make_uint4(pack_bf16x2(__uint_as_float(a.x), __uint_as_float(a.y)),
-                            pack_bf16x2(__uint_as_float(a.z), __uint_as_float(a.w)),
-                            pack_bf16x2(__uint_as_float(b.x), __uint_as_float(b.y)),
-                            pack_bf16x2(__uint_as_float(b.z), __uint_as_float(b.w))));
-}
-
-// one element as stored (no rounding: bf16 widens exactly)
-__device__ __forceinline__ float di_elem(const DiMat &m, int64_t row, int col) {
-  const char *rp = m.p + row * m.ld_bytes;
-  if (m.bf16) return bf16_to_f32(reinterpret_cast<const uint16_t *>(rp)[col]);
-  return reinterpret_cast<const float *>(rp)[col];
-}
-
-__device__ __forceinline__ void di_store(const DiOut &o, int64_t row, int col, float v) {
-  char *rp = o.p + row * o.ld_bytes;
-  if (o.bf16)
-    reinterpret_cast<uint16_t *>(rp)[col] = f32_to_bf16_rne(v);
-  else
-    reinterpret_cast<float *>(rp)[col] = v;
-}
-
 // this lane's fragments of the sample's tile: elements [16 s + 8 h, + 8) of vector r
 template <int D, int KS>
 __device__ __forceinline__ void di_load_tile(const DiArgs &p, int64_t b, bool live, int r, int h,
-                                             di_bf16x8 (&f)[KS]) {
+                                             bf16x8 (&f)[KS]) {
   const bool on = live && r < p.n && 8 * h < D;
   const bool from_bot = p.has_bot && r == 0;
   const int c0 = from_bot ? 0 : (r - p.has_bot) * D;
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
     if (!on)
-      f[s] = di_zero8();
+      f[s] = frag_zero8();
     else if (from_bot)
-      f[s] = di_load8(p.bot, b, 16 * s + 8 * h);
+      f[s] = mat_load8(p.bot, b, 16 * s + 8 * h);
     else
-      f[s] = di_load8(p.rows, b, c0 + 16 * s + 8 * h);
+      f[s] = mat_load8(p.rows, b, c0 + 16 * s + 8 * h);
   }
 }
 
@@ -124,17 +78,17 @@ __global__ __launch_bounds__(DI_THREADS) void dot_interact_fwd_kernel(DiArgs p) 
   const int filled = Dh + n * (n - 1) / 2;
   float *im = img[wave];
 
-  di_bf16x8 f[KS];
+  bf16x8 f[KS];
   di_load_tile<D, KS>(p, b, live, r, h, f);
-  di_f32x16 acc;
+  f32x16 acc;
 #pragma unroll
   for (int e = 0; e < 16; ++e) acc[e] = 0.f;
 #pragma unroll
-  for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[s], f[s], acc, 0, 0, 0);
+  for (int s = 0; s < KS; ++s) acc = mfma_32x32x16(f[s], f[s], acc);
 
   if (live) {
     if (p.has_bot)
-      for (int d = lane; d < D; d += 64) im[d] = di_elem(p.bot, b, d);
+      for (int d = lane; d < D; d += 64) im[d] = mat_elem(p.bot, b, d);
     // z[i, j], i = the register's row, j = this lane's column
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
@@ -195,10 +149,10 @@ __global__ __launch_bounds__(DI_THREADS) void dot_interact_bwd_kernel(DiArgs p) 
   const int Dh = p.has_bot ? D : 0;
   const int P = n * (n - 1) / 2;
 
-  di_bf16x8 f[KS];
+  bf16x8 f[KS];
   di_load_tile<D, KS>(p, b, live, r, h, f);
   if (live)
-    for (int q = lane; q < P; q += 64) tri[wave][q] = di_elem(p.dx, b, Dh + q);
+    for (int q = lane; q < P; q += 64) tri[wave][q] = mat_elem(p.dx, b, Dh + q);
   // T transposed, [d][vector]; vectors >= n are zeros
   if (8 * h < D) {
 #pragma unroll
@@ -209,7 +163,7 @@ __global__ __launch_bounds__(DI_THREADS) void dot_interact_bwd_kernel(DiArgs p) 
   __syncthreads();
   if (!live) return;
 
-  di_f32x16 Z[NCB];
+  f32x16 Z[NCB];
 #pragma unroll
   for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
@@ -234,13 +188,15 @@ __global__ __launch_bounds__(DI_THREADS) void dot_interact_bwd_kernel(DiArgs p) 
       cl[k] = pack_bf16x2(g[2 * k] - __uint_as_float(ch[k] << 16),
                           g[2 * k + 1] - __uint_as_float(ch[k] & 0xffff0000u));
     }
-    const di_bf16x8 a_hi = __builtin_bit_cast(di_bf16x8, make_uint4(ch[0], ch[1], ch[2], ch[3]));
-    const di_bf16x8 a_lo = __builtin_bit_cast(di_bf16x8, make_uint4(cl[0], cl[1], cl[2], cl[3]));
+    const bf16x8 a_hi = __builtin_bit_cast(bf16x8, make_uint4(ch[0], ch[1], ch[2], ch[3]));
+    const bf16x8 a_lo = __builtin_bit_cast(bf16x8, make_uint4(cl[0], cl[1], cl[2], cl[3]));
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
       const int d = 32 * cb + r;
-      di_bf16x8 bf = di_zero8();
-      if (d < D) bf = __builtin_bit_cast(di_bf16x8, *reinterpret_cast<const uint4 *>(&timg[wave][d][16 * s2 + 8 * h]));
+      bf16x8 bf = frag_zero8();
+      if (d < D) bf = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(&timg[wave][d][16 * s2 + 8 * h]));
+      // (the builtin, not mfma_32x32x16: through the wrapper the compiler orders this loop,
+      // with its conditional second product, differently)
       Z[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, bf, Z[cb], 0, 0, 0);
       if (split) Z[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo, bf, Z[cb], 0, 0, 0);
     }
@@ -256,9 +212,9 @@ __global__ __launch_bounds__(DI_THREADS) void dot_interact_bwd_kernel(DiArgs p) 
       const int i = (e & 3) + 8 * (e >> 2) + 4 * h;
       if (i >= n) continue;
       if (p.has_bot && i == 0)
-        di_store(p.dbot, b, d, Z[cb][e] + di_elem(p.dx, b, d));
+        mat_store(p.dbot, b, d, Z[cb][e] + mat_elem(p.dx, b, d));
       else
-        di_store(p.drows, b, (i - p.has_bot) * D + d, Z[cb][e]);
+        mat_store(p.drows, b, (i - p.has_bot) * D + d, Z[cb][e]);
     }
   }
 }
@@ -270,17 +226,11 @@ using namespace mrec;
 namespace {
 
 bool di_dim_ok(int32_t D) { return D == 8 || D == 16 || D == 32 || D == 64 || D == 128; }
-bool di_fdt(mrec_dtype t) { return t == MREC_F32 || t == MREC_BF16; }
-int64_t di_eb(mrec_dtype t) { return t == MREC_F32 ? 4 : 2; }
-
-// a [batch, >= cols] operand or output with 16-byte aligned rows
-bool di_mat_ok(const void *p, int64_t ld, int64_t cols, mrec_dtype t) {
-  return p && ld >= cols && (ld * di_eb(t)) % 16 == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0;
-}
 
 mrec_status di_check(const mrec_dot_interact_args *a, bool bwd, DiArgs &p) {
   MREC_CHECK_ARG(a, "NULL arguments");
-  MREC_CHECK_ARG(di_fdt(a->bot_dtype) && di_fdt(a->rows_dtype) && di_fdt(a->x_dtype) && di_fdt(a->dx_dtype),
+  MREC_CHECK_ARG(is_float_dtype(a->bot_dtype) && is_float_dtype(a->rows_dtype) &&
+                     is_float_dtype(a->x_dtype) && is_float_dtype(a->dx_dtype),
                  "unknown dtype: bot, rows, x and dx must each be MREC_F32 or MREC_BF16");
   MREC_CHECK_ARG(mrec_dot_interact_supported(a->D, a->n_fields, a->bot_dtype, a->rows_dtype, a->x_dtype, a->dx_dtype),
                  "unsupported shape (mrec_dot_interact_supported: D in {8, 16, 32, 64, 128}, 1 <= n_fields <= 31)");
@@ -290,28 +240,28 @@ mrec_status di_check(const mrec_dot_interact_args *a, bool bwd, DiArgs &p) {
   const int64_t Dh = has_bot ? a->D : 0, P = static_cast<int64_t>(n) * (n - 1) / 2;
   if (!bwd) MREC_CHECK_ARG(a->x_cols >= Dh + P, "x_cols smaller than D + P (the bottom vector and the pairs)");
   if (a->batch > 0) {
-    MREC_CHECK_ARG(!has_bot || di_mat_ok(a->bot, a->ld_bot, a->D, a->bot_dtype),
+    MREC_CHECK_ARG(!has_bot || rows16_ok(a->bot, a->ld_bot, a->D, a->bot_dtype),
                    "bot needs 16-byte aligned rows of at least D elements");
-    MREC_CHECK_ARG(di_mat_ok(a->rows, a->ld_rows, static_cast<int64_t>(a->n_fields) * a->D, a->rows_dtype),
+    MREC_CHECK_ARG(rows16_ok(a->rows, a->ld_rows, static_cast<int64_t>(a->n_fields) * a->D, a->rows_dtype),
                    "rows needs 16-byte aligned rows of at least n_fields * D elements");
     if (!bwd) {
-      MREC_CHECK_ARG(di_mat_ok(a->x, a->ld_x, a->x_cols, a->x_dtype),
+      MREC_CHECK_ARG(rows16_ok(a->x, a->ld_x, a->x_cols, a->x_dtype),
                      "x needs 16-byte aligned rows of at least x_cols elements");
     } else {
-      MREC_CHECK_ARG(di_mat_ok(a->dx, a->ld_dx, Dh + P, a->dx_dtype),
+      MREC_CHECK_ARG(rows16_ok(a->dx, a->ld_dx, Dh + P, a->dx_dtype),
                      "dx needs 16-byte aligned rows of at least D + P elements");
-      MREC_CHECK_ARG(!has_bot || di_mat_ok(a->dbot, a->ld_dbot, a->D, a->bot_dtype),
+      MREC_CHECK_ARG(!has_bot || rows16_ok(a->dbot, a->ld_dbot, a->D, a->bot_dtype),
                      "dbot needs 16-byte aligned rows of at least D elements");
-      MREC_CHECK_ARG(di_mat_ok(a->drows, a->ld_drows, static_cast<int64_t>(a->n_fields) * a->D, a->rows_dtype),
+      MREC_CHECK_ARG(rows16_ok(a->drows, a->ld_drows, static_cast<int64_t>(a->n_fields) * a->D, a->rows_dtype),
                      "drows needs 16-byte aligned rows of at least n_fields * D elements");
     }
   }
-  p.bot = DiMat{static_cast<const char *>(a->bot), a->ld_bot * di_eb(a->bot_dtype), a->bot_dtype == MREC_BF16};
-  p.rows = DiMat{static_cast<const char *>(a->rows), a->ld_rows * di_eb(a->rows_dtype), a->rows_dtype == MREC_BF16};
-  p.dx = DiMat{static_cast<const char *>(a->dx), a->ld_dx * di_eb(a->dx_dtype), a->dx_dtype == MREC_BF16};
-  p.x = DiOut{static_cast<char *>(a->x), a->ld_x * di_eb(a->x_dtype), a->x_dtype == MREC_BF16};
-  p.dbot = DiOut{static_cast<char *>(a->dbot), a->ld_dbot * di_eb(a->bot_dtype), a->bot_dtype == MREC_BF16};
-  p.drows = DiOut{static_cast<char *>(a->drows), a->ld_drows * di_eb(a->rows_dtype), a->rows_dtype == MREC_BF16};
+  p.bot = mat_in(a->bot, a->ld_bot, a->bot_dtype);
+  p.rows = mat_in(a->rows, a->ld_rows, a->rows_dtype);
+  p.dx = mat_in(a->dx, a->ld_dx, a->dx_dtype);
+  p.x = mat_out(a->x, a->ld_x, a->x_dtype);
+  p.dbot = mat_out(a->dbot, a->ld_dbot, a->bot_dtype);
+  p.drows = mat_out(a->drows, a->ld_drows, a->rows_dtype);
   p.B = a->batch;
   p.x_cols = a->x_cols;
   p.n = n;
@@ -350,8 +300,8 @@ extern "C" {
 
 int32_t mrec_dot_interact_supported(int32_t D, int32_t n_fields, mrec_dtype bot_dtype, mrec_dtype rows_dtype,
                                     mrec_dtype x_dtype, mrec_dtype dx_dtype) {
-  return di_dim_ok(D) && n_fields >= 1 && n_fields <= 31 && di_fdt(bot_dtype) && di_fdt(rows_dtype) &&
-         di_fdt(x_dtype) && di_fdt(dx_dtype);
+  return di_dim_ok(D) && n_fields >= 1 && n_fields <= 31 && is_float_dtype(bot_dtype) &&
+         is_float_dtype(rows_dtype) && is_float_dtype(x_dtype) && is_float_dtype(dx_dtype);
 }
 
 mrec_status mrec_dot_interact_fwd(const mrec_dot_interact_args *a, mrec_stream stream) {

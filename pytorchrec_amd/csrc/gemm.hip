@@ -27,6 +27,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "frag.h"
 #include "gemm_common.h"
 #include "head_common.h"
 
@@ -41,11 +42,6 @@ constexpr int KG = 64;                 // k per staging group
 constexpr int NBUF = MREC_GEMM_NBUF;   // k-group ring depth, 16 KiB per group: 3 -> 48 KiB, 3 WG/CU (4: +3%, 5: +5%, 6: +50% measured)
 constexpr int GROUP_ELEMS = 64 * KG;   // one operand's group image (bf16 elements)
 constexpr int TLD = BN + 4;            // fp32 row stride of the C tile staged in LDS
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4s lds_v4s;
 
 __device__ __attribute__((aligned(64))) uint4 g_zero_page[64];
 
@@ -286,24 +282,20 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs &g, int bx, int bz, uin
           a[i] = *reinterpret_cast<const bf16x8 *>(ag + aoff[s] + i * 16 * KG);
         } else {
           const uint16_t *q = ag + aoff[s] + i * 128;
-          const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s *)(q));
-          const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s *)(q + 64));
-          a[i] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+          a[i] = lds_tr16_pair(q, 64);
         }
         if constexpr (!B_COL) {
           b[i] = *reinterpret_cast<const bf16x8 *>(bg + boff[s] + i * 16 * KG);
         } else {
           const uint16_t *q = bg + boff[s] + i * 128;
-          const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s *)(q));
-          const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s *)(q + 64));
-          b[i] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+          b[i] = lds_tr16_pair(q, 64);
         }
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
+          acc[i][j] = mfma_16x16x32(a[i], b[j], acc[i][j]);
     }
   }
 

@@ -45,13 +45,9 @@
 // bits.  his_len outside 1..L (or an order entry outside the batch) sets *d_oob_flag and
 // is clamped: nothing is read or written out of bounds, length 0 gives h_last = 0.
 #include "common.h"
+#include "frag.h"
 
 namespace mrec {
-
-typedef short gr_bf16x8 __attribute__((ext_vector_type(8)));
-typedef short gr_bf16x4 __attribute__((ext_vector_type(4)));
-typedef float gr_f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t gr_u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int GR_TILE = 16;  // samples per workgroup tile (the MFMA's rows)
 constexpr int GR_MAXL = 64;
@@ -92,21 +88,6 @@ struct GrShape {
   static constexpr int XI = (GR_TILE * CHX + NT - 1) / NT;  // x chunks a thread stages
 };
 
-__device__ __forceinline__ gr_bf16x8 gr_zero8() { return gr_bf16x8{0, 0, 0, 0, 0, 0, 0, 0}; }
-
-__device__ __forceinline__ gr_bf16x8 gr_pack8(const float *f) {
-  const gr_u32x4 u = {pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]),
-                      pack_bf16x2(f[6], f[7])};
-  return __builtin_bit_cast(gr_bf16x8, u);
-}
-
-__device__ __forceinline__ gr_f32x4 gr_mfma32(gr_bf16x8 a, gr_bf16x8 b, gr_f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ gr_f32x4 gr_mfma16(gr_bf16x4 a, gr_bf16x4 b, gr_f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0);
-}
-
 // sigmoid = 1 / (1 + exp(-x)), tanh = 1 - 2 / (1 + exp(2x)): both forms go to their limits
 // without inf / inf for large |x| (exp -> inf gives rcp -> 0).  v_exp_f32 and v_rcp_f32
 // (1 ulp each): the gate math is the step's VALU work, 12 activations per lane, and libm's
@@ -123,43 +104,33 @@ __device__ __forceinline__ float gr_tanh(float x) {
 
 // fragment of W[n0 + (lane & 15)][k0 + 8 (lane >> 4) .. + 8] (zero past `cols`): the B
 // operand of a product over W's columns, from the fp32 master
-__device__ __forceinline__ gr_bf16x8 gr_wfrag(const float *w, int64_t ld, int n0, int k0, int cols,
-                                              int lane) {
+__device__ __forceinline__ bf16x8 gr_wfrag(const float *w, int64_t ld, int n0, int k0, int cols,
+                                           int lane) {
   const int k = k0 + 8 * (lane >> 4);
-  if (k >= cols) return gr_zero8();
+  if (k >= cols) return frag_zero8();
   const float *p = w + (n0 + (lane & 15)) * ld + k;
   float f[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) f[i] = p[i];
-  return gr_pack8(f);
+  return frag_pack8(f);
 }
 
 // fragment of W^T: element i is W[k0 + 8 (lane >> 4) + i][n0 + (lane & 15)] (zero past
 // `rows`): the B operand of a product over W's rows
-__device__ __forceinline__ gr_bf16x8 gr_wfrag_t(const float *w, int64_t ld, int n0, int k0, int rows,
-                                                int lane) {
+__device__ __forceinline__ bf16x8 gr_wfrag_t(const float *w, int64_t ld, int n0, int k0, int rows,
+                                             int lane) {
   const int k = k0 + 8 * (lane >> 4);
   float f[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) f[i] = k + i < rows ? w[(k + i) * ld + n0 + (lane & 15)] : 0.f;
-  return gr_pack8(f);
+  return frag_pack8(f);
 }
 
 // A fragment of rows 0..15, k0 .. k0 + 31 of a bf16 [16][ld] LDS tile `cols` wide
-__device__ __forceinline__ gr_bf16x8 gr_afrag(const uint16_t *tile, int ld, int k0, int cols, int lane) {
+__device__ __forceinline__ bf16x8 gr_afrag(const uint16_t *tile, int ld, int k0, int cols, int lane) {
   const int k = k0 + 8 * (lane >> 4);
-  if (k >= cols) return gr_zero8();
-  return *reinterpret_cast<const gr_bf16x8 *>(tile + (lane & 15) * ld + k);
-}
-
-// transposing fragment for the k = 16 MFMA: element j is tile[4 (lane >> 4) + j][c0 +
-// (lane & 15)].  ds_read_b64_tr_b16: per 16-lane group, lane 4 q + p addresses row q,
-// columns 4 p .. + 3 of a 4 x 16 block and lane i receives column i.  Every lane of the
-// wave takes part (callers branch per wave only); every address lies inside the tile.
-__device__ __forceinline__ gr_bf16x4 gr_tr(const uint16_t *tile, int ld, int c0, int lane) {
-  const int li = lane & 15;
-  const uint16_t *p = tile + (4 * (lane >> 4) + (li >> 2)) * ld + c0 + 4 * (li & 3);
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) gr_bf16x4 *)(p));
+  if (k >= cols) return frag_zero8();
+  return *reinterpret_cast<const bf16x8 *>(tile + (lane & 15) * ld + k);
 }
 
 // sample and clamped length of the tile's 16 slots -> LDS (slot past the batch: -1, 0);
@@ -203,7 +174,7 @@ __global__ __launch_bounds__(64 * (H / 16)) void gru_fwd_kernel(GruArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int a = lane & 15, q = lane >> 4;
   const int u = 16 * wave + a;  // this lane's hidden unit
-  gr_bf16x8 wi[3][S::KSE], wh[3][S::KSH];
+  bf16x8 wi[3][S::KSE], wh[3][S::KSH];
 #pragma unroll
   for (int g = 0; g < 3; ++g) {
 #pragma unroll
@@ -229,32 +200,32 @@ __global__ __launch_bounds__(64 * (H / 16)) void gru_fwd_kernel(GruArgs p) {
     for (int i = tid; i < GR_TILE * S::LDH / 8; i += S::NT)
       reinterpret_cast<uint4 *>(s_h[0])[i] = make_uint4(0, 0, 0, 0);
     __syncthreads();
-    auto load_x = [&](int t, gr_bf16x8 *xf) {
+    auto load_x = [&](int t, bf16x8 *xf) {
 #pragma unroll
       for (int s = 0; s < S::KSE; ++s) {
-        xf[s] = gr_zero8();
+        xf[s] = frag_zero8();
         if (32 * s + 8 * q < E && t < lenA)
-          xf[s] = *reinterpret_cast<const gr_bf16x8 *>(xrow + t * p.ld_rows + 32 * s);
+          xf[s] = *reinterpret_cast<const bf16x8 *>(xrow + t * p.ld_rows + 32 * s);
       }
     };
-    gr_bf16x8 xf[S::KSE], xn[S::KSE];
+    bf16x8 xf[S::KSE], xn[S::KSE];
     load_x(0, xf);
     for (int t = 0; t < tmax; ++t) {
       load_x(t + 1, xn);  // (t + 1 >= lenA: no load)
-      gr_f32x4 ar = {0.f, 0.f, 0.f, 0.f}, az = ar, anx = ar, anh = ar;
+      f32x4 ar = {0.f, 0.f, 0.f, 0.f}, az = ar, anx = ar, anh = ar;
 #pragma unroll
       for (int s = 0; s < S::KSE; ++s) {
-        ar = gr_mfma32(xf[s], wi[0][s], ar);
-        az = gr_mfma32(xf[s], wi[1][s], az);
-        anx = gr_mfma32(xf[s], wi[2][s], anx);
+        ar = mfma_16x16x32(xf[s], wi[0][s], ar);
+        az = mfma_16x16x32(xf[s], wi[1][s], az);
+        anx = mfma_16x16x32(xf[s], wi[2][s], anx);
       }
       const uint16_t *hc = s_h[t & 1];
 #pragma unroll
       for (int s = 0; s < S::KSH; ++s) {
-        const gr_bf16x8 hf = gr_afrag(hc, S::LDH, 32 * s, H, lane);
-        ar = gr_mfma32(hf, wh[0][s], ar);
-        az = gr_mfma32(hf, wh[1][s], az);
-        anh = gr_mfma32(hf, wh[2][s], anh);
+        const bf16x8 hf = gr_afrag(hc, S::LDH, 32 * s, H, lane);
+        ar = mfma_16x16x32(hf, wh[0][s], ar);
+        az = mfma_16x16x32(hf, wh[1][s], az);
+        anh = mfma_16x16x32(hf, wh[2][s], anh);
       }
       uint16_t *hn = s_h[(t + 1) & 1];
 #pragma unroll
@@ -293,7 +264,7 @@ __global__ __launch_bounds__(64 * (H / 16)) void gru_bwd_kernel(GruArgs p) {
   const int a = lane & 15, q = lane >> 4;
   const int u = 16 * wave + a;
   // the weights in both orientations
-  gr_bf16x8 wi[3][S::KSE], wh[3][S::KSH], wiT[S::CTW][S::KSG], whT[S::KSG];
+  bf16x8 wi[3][S::KSE], wh[3][S::KSH], wiT[S::CTW][S::KSG], whT[S::KSG];
 #pragma unroll
   for (int g = 0; g < 3; ++g) {
 #pragma unroll
@@ -307,18 +278,18 @@ __global__ __launch_bounds__(64 * (H / 16)) void gru_bwd_kernel(GruArgs p) {
 #pragma unroll
     for (int ci = 0; ci < S::CTW; ++ci) {
       const int c = wave + S::NW * ci;
-      wiT[ci][s] = c < S::CT ? gr_wfrag_t(p.w_ih, p.ld_ih, 16 * c, 32 * s, 3 * H, lane) : gr_zero8();
+      wiT[ci][s] = c < S::CT ? gr_wfrag_t(p.w_ih, p.ld_ih, 16 * c, 32 * s, 3 * H, lane) : frag_zero8();
     }
   }
   const float br = p.b_ih[u] + p.b_hh[u], bz = p.b_ih[H + u] + p.b_hh[H + u];
   const float bnx = p.b_ih[2 * H + u], bnh = p.b_hh[2 * H + u];
-  gr_f32x4 dwi[3][S::CT], dwh[3][S::NW];
+  f32x4 dwi[3][S::CT], dwh[3][S::NW];
 #pragma unroll
   for (int g = 0; g < 3; ++g) {
 #pragma unroll
-    for (int c = 0; c < S::CT; ++c) dwi[g][c] = gr_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < S::CT; ++c) dwi[g][c] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int c = 0; c < S::NW; ++c) dwh[g][c] = gr_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < S::NW; ++c) dwh[g][c] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   float db[4] = {0.f, 0.f, 0.f, 0.f};  // sums of da_r, da_z, da_n, da_n r over this lane's rows
   // the dG tiles' padding columns (3H .. KG) stay zero
@@ -384,20 +355,20 @@ __global__ __launch_bounds__(64 * (H / 16)) void gru_bwd_kernel(GruArgs p) {
     for (int t = tmax - 1; t >= 0; --t) {
       __syncthreads();  // step t's staged tiles are visible; the dG tiles are free
       // the forward's gates, recomputed
-      gr_f32x4 ar = {0.f, 0.f, 0.f, 0.f}, az = ar, anx = ar, anh = ar;
+      f32x4 ar = {0.f, 0.f, 0.f, 0.f}, az = ar, anx = ar, anh = ar;
 #pragma unroll
       for (int s = 0; s < S::KSE; ++s) {
-        const gr_bf16x8 xf = gr_afrag(s_x[buf], S::LDX, 32 * s, E, lane);
-        ar = gr_mfma32(xf, wi[0][s], ar);
-        az = gr_mfma32(xf, wi[1][s], az);
-        anx = gr_mfma32(xf, wi[2][s], anx);
+        const bf16x8 xf = gr_afrag(s_x[buf], S::LDX, 32 * s, E, lane);
+        ar = mfma_16x16x32(xf, wi[0][s], ar);
+        az = mfma_16x16x32(xf, wi[1][s], az);
+        anx = mfma_16x16x32(xf, wi[2][s], anx);
       }
 #pragma unroll
       for (int s = 0; s < S::KSH; ++s) {
-        const gr_bf16x8 hf = gr_afrag(s_h[buf], S::LDH, 32 * s, H, lane);
-        ar = gr_mfma32(hf, wh[0][s], ar);
-        az = gr_mfma32(hf, wh[1][s], az);
-        anh = gr_mfma32(hf, wh[2][s], anh);
+        const bf16x8 hf = gr_afrag(s_h[buf], S::LDH, 32 * s, H, lane);
+        ar = mfma_16x16x32(hf, wh[0][s], ar);
+        az = mfma_16x16x32(hf, wh[1][s], az);
+        anh = mfma_16x16x32(hf, wh[2][s], anh);
       }
       float zk[4];
 #pragma unroll
@@ -425,10 +396,10 @@ __global__ __launch_bounds__(64 * (H / 16)) void gru_bwd_kernel(GruArgs p) {
       if (t > 0) stage_load(t - 1);  // in flight over the products below
       __syncthreads();
       // dh <- dh z + dGh W_hh
-      gr_f32x4 adh = {0.f, 0.f, 0.f, 0.f};
+      f32x4 adh = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int s = 0; s < S::KSG; ++s)
-        adh = gr_mfma32(gr_afrag(s_gh, S::LDG, 32 * s, S::KG, lane), whT[s], adh);
+        adh = mfma_16x16x32(gr_afrag(s_gh, S::LDG, 32 * s, S::KG, lane), whT[s], adh);
 #pragma unroll
       for (int e = 0; e < 4; ++e) dh[e] = t < lenC[e] ? dh[e] * zk[e] + adh[e] : dh[e];
       // dx_t = dGx W_ih
@@ -436,10 +407,10 @@ __global__ __launch_bounds__(64 * (H / 16)) void gru_bwd_kernel(GruArgs p) {
       for (int ci = 0; ci < S::CTW; ++ci) {
         const int c = wave + S::NW * ci;
         if (c < S::CT) {
-          gr_f32x4 adx = {0.f, 0.f, 0.f, 0.f};
+          f32x4 adx = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int s = 0; s < S::KSG; ++s)
-            adx = gr_mfma32(gr_afrag(s_gx, S::LDG, 32 * s, S::KG, lane), wiT[ci][s], adx);
+            adx = mfma_16x16x32(gr_afrag(s_gx, S::LDG, 32 * s, S::KG, lane), wiT[ci][s], adx);
 #pragma unroll
           for (int e = 0; e < 4; ++e)
             if (t < lenC[e])
@@ -447,22 +418,22 @@ __global__ __launch_bounds__(64 * (H / 16)) void gru_bwd_kernel(GruArgs p) {
         }
       }
       // dW_ih += dGx^T x_t, dW_hh += dGh^T h_{t-1} (h_-1 = 0: nothing at t = 0)
-      gr_bf16x4 xT[S::CT], hT[S::NW];
+      bf16x4 xT[S::CT], hT[S::NW];
 #pragma unroll
-      for (int c = 0; c < S::CT; ++c) xT[c] = gr_tr(s_x[buf], S::LDX, 16 * c, lane);
+      for (int c = 0; c < S::CT; ++c) xT[c] = lds_tr16x4(s_x[buf], S::LDX, 16 * c, lane);
       if (t > 0) {
 #pragma unroll
-        for (int c = 0; c < S::NW; ++c) hT[c] = gr_tr(s_h[buf], S::LDH, 16 * c, lane);
+        for (int c = 0; c < S::NW; ++c) hT[c] = lds_tr16x4(s_h[buf], S::LDH, 16 * c, lane);
       }
 #pragma unroll
       for (int g = 0; g < 3; ++g) {
-        const gr_bf16x4 gxT = gr_tr(s_gx, S::LDG, g * H + 16 * wave, lane);
+        const bf16x4 gxT = lds_tr16x4(s_gx, S::LDG, g * H + 16 * wave, lane);
 #pragma unroll
-        for (int c = 0; c < S::CT; ++c) dwi[g][c] = gr_mfma16(gxT, xT[c], dwi[g][c]);
+        for (int c = 0; c < S::CT; ++c) dwi[g][c] = mfma_16x16x16(gxT, xT[c], dwi[g][c]);
         if (t > 0) {
-          const gr_bf16x4 ghT = gr_tr(s_gh, S::LDG, g * H + 16 * wave, lane);
+          const bf16x4 ghT = lds_tr16x4(s_gh, S::LDG, g * H + 16 * wave, lane);
 #pragma unroll
-          for (int c = 0; c < S::NW; ++c) dwh[g][c] = gr_mfma16(ghT, hT[c], dwh[g][c]);
+          for (int c = 0; c < S::NW; ++c) dwh[g][c] = mfma_16x16x16(ghT, hT[c], dwh[g][c]);
         }
       }
       if (t > 0) stage_store(buf ^ 1);
@@ -500,18 +471,6 @@ __global__ __launch_bounds__(64 * (H / 16)) void gru_bwd_kernel(GruArgs p) {
 using namespace mrec;
 
 namespace {
-
-int gr_cus() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      v = 256;
-    (void)hipGetLastError();
-    return v;
-  }();
-  return n;
-}
 
 bool gr_aligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -563,7 +522,7 @@ int32_t mrec_gru_supported(int32_t E, int32_t H, int32_t L) {
 int32_t mrec_gru_tile(void) { return GR_TILE; }
 
 int64_t mrec_gru_parts(int64_t batch) {
-  const int64_t g = gr_cus(), tiles = (batch + GR_TILE - 1) / GR_TILE;
+  const int64_t g = device_cus(), tiles = (batch + GR_TILE - 1) / GR_TILE;
   return tiles < g ? (tiles > 0 ? tiles : 1) : g;
 }
 

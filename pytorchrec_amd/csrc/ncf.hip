@@ -158,9 +158,9 @@ __global__ __launch_bounds__(NC_THREADS) void ncf_bwd_kernel(NcfArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int a = lane & 15, q = lane >> 4;
   nc_stage(p, sm, sf, tid, true);
-  nc_f32x4 dw[NC_MAXT];
+  f32x4 dw[NC_MAXT];
 #pragma unroll
-  for (int t = 0; t < NC_MAXT; ++t) dw[t] = nc_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < NC_MAXT; ++t) dw[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   // db of the layers below the last (this wave's 16 pairs, every unit), the last layer's
   // db and dwp[E:] (this wave's units, all 64 pairs), dwp[:E] (this wave's 16 pairs)
   float db[NC_MAXL][NC_MAXNT], dbl[2] = {0.f, 0.f}, dwph[2] = {0.f, 0.f}, dwpg[2][8];
@@ -232,10 +232,10 @@ __global__ __launch_bounds__(NC_THREADS) void ncf_bwd_kernel(NcfArgs p) {
 #pragma unroll
         for (int ct = 0; ct < NC_MAXNT; ++ct) {
           if (ct < p.CT[l]) {
-            nc_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
             for (int nt = 0; nt < p.NT[l]; ++nt)
-              acc = nc_mfma16(*reinterpret_cast<const nc_bf16x4 *>(zin + 16 * nt),
-                              nc_tr(W + 16 * nt * ldw, ldw, 16 * ct, lane), acc);
+              acc = mfma_16x16x16(*reinterpret_cast<const bf16x4 *>(zin + 16 * nt),
+                                  lds_tr16x4(W + 16 * nt * ldw, ldw, 16 * ct, lane), acc);
             const int col = 16 * ct + a;
             if (l > 0) {
 #pragma unroll
@@ -270,8 +270,8 @@ __global__ __launch_bounds__(NC_THREADS) void ncf_bwd_kernel(NcfArgs p) {
         const int zc = tab[5 * g], hc = tab[5 * g + 1];
 #pragma unroll
         for (int blk = 0; blk < NC_TILE / 16; ++blk)
-          dw[t] = nc_mfma16(nc_tr(Za + 16 * blk * p.ldz, p.ldz, zc, lane),
-                            nc_tr(Ha + 16 * blk * p.lda, p.lda, hc, lane), dw[t]);
+          dw[t] = mfma_16x16x16(lds_tr16x4(Za + 16 * blk * p.ldz, p.ldz, zc, lane),
+                                lds_tr16x4(Ha + 16 * blk * p.lda, p.lda, hc, lane), dw[t]);
       }
     }
   }
@@ -361,18 +361,6 @@ __global__ __launch_bounds__(NC_THREADS) void ncf_bwd_kernel(NcfArgs p) {
 using namespace mrec;
 
 namespace {
-
-int nc_cus() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      v = 256;
-    (void)hipGetLastError();
-    return v;
-  }();
-  return n;
-}
 
 bool nc_aligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -473,7 +461,7 @@ int32_t mrec_ncf_supported(int32_t E, int32_t n_layers, const int32_t *widths) {
 int32_t mrec_ncf_tile(void) { return NC_TILE; }
 
 int64_t mrec_ncf_parts(int64_t pairs) {
-  const int64_t g = nc_cus(), tiles = (pairs + NC_TILE - 1) / NC_TILE;
+  const int64_t g = device_cus(), tiles = (pairs + NC_TILE - 1) / NC_TILE;
   return tiles < g ? (tiles > 0 ? tiles : 1) : g;
 }
 

@@ -5,12 +5,9 @@
 #pragma once
 
 #include "common.h"
+#include "frag.h"
 
 namespace mrec {
-
-typedef short nc_bf16x8 __attribute__((ext_vector_type(8)));
-typedef short nc_bf16x4 __attribute__((ext_vector_type(4)));
-typedef float nc_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int NC_TILE = 64;      // pairs per tile: four row blocks of 16
 constexpr int NC_THREADS = 256;
@@ -48,23 +45,6 @@ struct NcfArgs {
   // the partial's sections
   int woff[NC_MAXL + 1], dboff[NC_MAXL + 1], dwpoff;
 };
-
-__device__ __forceinline__ nc_f32x4 nc_mfma32(nc_bf16x8 a, nc_bf16x8 b, nc_f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ nc_f32x4 nc_mfma16(nc_bf16x4 a, nc_bf16x4 b, nc_f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0);
-}
-
-// transposing fragment for the k = 16 MFMA: element j is tile[4 (lane >> 4) + j][c0 +
-// (lane & 15)].  ds_read_b64_tr_b16: per 16-lane group, lane 4 q + p addresses row q,
-// columns 4 p .. + 3 of a 4 x 16 block and lane i receives column i.  Every lane of the
-// wave takes part (callers branch per wave only); every address lies inside the tile.
-__device__ __forceinline__ nc_bf16x4 nc_tr(const uint16_t *tile, int ld, int c0, int lane) {
-  const int li = lane & 15;
-  const uint16_t *p = tile + (4 * (lane >> 4) + (li >> 2)) * ld + c0 + 4 * (li & 3);
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) nc_bf16x4 *)(p));
-}
 
 // Once per workgroup: the weight images (bf16, zero padded), biases, wp, zeroed arenas,
 // the dW tile table, by a workgroup of `threads` threads.  Ends at a barrier.
@@ -145,27 +125,27 @@ __device__ __forceinline__ void nc_mlp(const NcfArgs &p, uint16_t *sm, float *sf
         for (int e = 0; e < 4; ++e) dot[rb][e] = 0.f;
       }
       if (has0) {
-        nc_f32x4 acc[2][NRB];
+        f32x4 acc[2][NRB];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
 #pragma unroll
-          for (int rb = 0; rb < NRB; ++rb) acc[j][rb] = nc_f32x4{0.f, 0.f, 0.f, 0.f};
+          for (int rb = 0; rb < NRB; ++rb) acc[j][rb] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
         const uint16_t *hin = H + a * p.lda + p.hoff[l] + 8 * q;
         const uint16_t *w0 = W + (16 * wave + a) * ldw + 8 * q;
         const uint16_t *w1 = w0 + 64 * ldw;
         for (int ks = 0; ks < p.KS[l]; ++ks) {
-          nc_bf16x8 af[NRB];
+          bf16x8 af[NRB];
 #pragma unroll
           for (int rb = 0; rb < NRB; ++rb)
-            af[rb] = *reinterpret_cast<const nc_bf16x8 *>(hin + 16 * (rb0 + rb) * p.lda + 32 * ks);
-          const nc_bf16x8 b0 = *reinterpret_cast<const nc_bf16x8 *>(w0 + 32 * ks);
+            af[rb] = *reinterpret_cast<const bf16x8 *>(hin + 16 * (rb0 + rb) * p.lda + 32 * ks);
+          const bf16x8 b0 = *reinterpret_cast<const bf16x8 *>(w0 + 32 * ks);
 #pragma unroll
-          for (int rb = 0; rb < NRB; ++rb) acc[0][rb] = nc_mfma32(af[rb], b0, acc[0][rb]);
+          for (int rb = 0; rb < NRB; ++rb) acc[0][rb] = mfma_16x16x32(af[rb], b0, acc[0][rb]);
           if (has1) {
-            const nc_bf16x8 b1 = *reinterpret_cast<const nc_bf16x8 *>(w1 + 32 * ks);
+            const bf16x8 b1 = *reinterpret_cast<const bf16x8 *>(w1 + 32 * ks);
 #pragma unroll
-            for (int rb = 0; rb < NRB; ++rb) acc[1][rb] = nc_mfma32(af[rb], b1, acc[1][rb]);
+            for (int rb = 0; rb < NRB; ++rb) acc[1][rb] = mfma_16x16x32(af[rb], b1, acc[1][rb]);
           }
         }
 #pragma unroll

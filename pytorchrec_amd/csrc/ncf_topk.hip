@@ -60,28 +60,6 @@ struct NcfTopkArgs {
   TkOut o;
 };
 
-// 8 consecutive elements of a bank row as bf16 (an fp32 bank is rounded here)
-template <typename T>
-__device__ __forceinline__ uint4 nt_load8(const char *p) {
-  if constexpr (sizeof(T) == 2) {
-    return *reinterpret_cast<const uint4 *>(p);
-  } else {
-    const uint4 a = *reinterpret_cast<const uint4 *>(p), b = *reinterpret_cast<const uint4 *>(p + 16);
-    return make_uint4(pack_bf16x2(__uint_as_float(a.x), __uint_as_float(a.y)),
-                      pack_bf16x2(__uint_as_float(a.z), __uint_as_float(a.w)),
-                      pack_bf16x2(__uint_as_float(b.x), __uint_as_float(b.y)),
-                      pack_bf16x2(__uint_as_float(b.z), __uint_as_float(b.w)));
-  }
-}
-// one element of a bank row as its bf16 value
-template <typename T>
-__device__ __forceinline__ float nt_elem(const char *row, int e) {
-  if constexpr (sizeof(T) == 2)
-    return bf16_to_f32(reinterpret_cast<const uint16_t *>(row)[e]);
-  else
-    return bf16_to_f32(f32_to_bf16_rne(reinterpret_cast<const float *>(row)[e]));
-}
-
 template <typename T>
 __global__ __launch_bounds__(NT_THREADS) void ncf_topk_kernel(NcfTopkArgs p) {
   extern __shared__ __attribute__((aligned(16))) char nt_lds[];
@@ -130,8 +108,8 @@ __global__ __launch_bounds__(NT_THREADS) void ncf_topk_kernel(NcfTopkArgs p) {
   for (int i = tid; i < NT_TU * E; i += NT_THREADS) {
     const int u = i / E, e = i - u * E;
     const int64_t row = urow[u];
-    sf[p.muoff + i] = row >= 0 ? nt_elem<T>(p.tab[0] + row * p.row_bytes, e) : 0.f;
-    sf[p.coff + i] = row >= 0 ? nt_elem<T>(p.tab[2] + row * p.row_bytes, e) : 0.f;
+    sf[p.muoff + i] = row >= 0 ? elem_bf16<T>(p.tab[0] + row * p.row_bytes, e) : 0.f;
+    sf[p.coff + i] = row >= 0 ? elem_bf16<T>(p.tab[2] + row * p.row_bytes, e) : 0.f;
   }
   __syncthreads();
   for (int i = tid; i < NT_TU * n16; i += NT_THREADS) {
@@ -169,7 +147,7 @@ __global__ __launch_bounds__(NT_THREADS) void ncf_topk_kernel(NcfTopkArgs p) {
     for (int i = tid; i < NT_TI * chunks; i += NT_THREADS) {
       const int row = i / chunks, c = i - row * chunks;
       uint4 v = make_uint4(0, 0, 0, 0);
-      if (base + row < p.high) v = nt_load8<T>(p.tab[3] + (base + row) * p.row_bytes + 8 * c * eb);
+      if (base + row < p.high) v = load8_bf16<T>(p.tab[3] + (base + row) * p.row_bytes + 8 * c * eb);
       *reinterpret_cast<uint4 *>(H + row * m.lda + m.hoff[0] + 8 * c) = v;
     }
     const int64_t item = base + 16 * wave + a;
@@ -178,34 +156,34 @@ __global__ __launch_bounds__(NT_THREADS) void ncf_topk_kernel(NcfTopkArgs p) {
     for (int i = 0; i < 2; ++i) {
       const int c = q + 4 * i;
       mv[i] = make_uint4(0, 0, 0, 0);
-      if (c < chunks && item < p.high && tid < NC_THREADS) mv[i] = nt_load8<T>(p.tab[1] + item * p.row_bytes + 8 * c * eb);
+      if (c < chunks && item < p.high && tid < NC_THREADS) mv[i] = load8_bf16<T>(p.tab[1] + item * p.row_bytes + 8 * c * eb);
     }
     __syncthreads();
     // c = mlp_i W_0[:, E:]^T: the wave's output tiles and row blocks as in a layer of
     // nc_mlp; fp32 to LDS, no bias, no ReLU
     if (wave < m.NT[0]) {
       const bool has1 = wave + 4 < m.NT[0];
-      nc_f32x4 acc[2][2];
+      f32x4 acc[2][2];
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
 #pragma unroll
-        for (int rb = 0; rb < 2; ++rb) acc[j][rb] = nc_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int rb = 0; rb < 2; ++rb) acc[j][rb] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
       const uint16_t *hin = H + (16 * rb0 + a) * m.lda + m.hoff[0] + 8 * q;
       const uint16_t *w0 = sm + m.wimg[0] + (16 * wave + a) * m.ldw[0] + 8 * q;
       const uint16_t *w1 = w0 + 64 * m.ldw[0];
       for (int ks = 0; ks < m.KS[0]; ++ks) {
-        nc_bf16x8 af[2];
+        bf16x8 af[2];
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
-          af[rb] = *reinterpret_cast<const nc_bf16x8 *>(hin + 16 * rb * m.lda + 32 * ks);
-        const nc_bf16x8 f0 = *reinterpret_cast<const nc_bf16x8 *>(w0 + 32 * ks);
+          af[rb] = *reinterpret_cast<const bf16x8 *>(hin + 16 * rb * m.lda + 32 * ks);
+        const bf16x8 f0 = *reinterpret_cast<const bf16x8 *>(w0 + 32 * ks);
 #pragma unroll
-        for (int rb = 0; rb < 2; ++rb) acc[0][rb] = nc_mfma32(af[rb], f0, acc[0][rb]);
+        for (int rb = 0; rb < 2; ++rb) acc[0][rb] = mfma_16x16x32(af[rb], f0, acc[0][rb]);
         if (has1) {
-          const nc_bf16x8 f1 = *reinterpret_cast<const nc_bf16x8 *>(w1 + 32 * ks);
+          const bf16x8 f1 = *reinterpret_cast<const bf16x8 *>(w1 + 32 * ks);
 #pragma unroll
-          for (int rb = 0; rb < 2; ++rb) acc[1][rb] = nc_mfma32(af[rb], f1, acc[1][rb]);
+          for (int rb = 0; rb < 2; ++rb) acc[1][rb] = mfma_16x16x32(af[rb], f1, acc[1][rb]);
         }
       }
 #pragma unroll
@@ -390,7 +368,7 @@ int32_t mrec_ncf_topk_splits(int64_t batch, int64_t n_items) {
   const int64_t ut = (batch + NT_TU - 1) / NT_TU, it = (n_items + NT_TI - 1) / NT_TI;
   // fill the CUs when the batch is small; c is recomputed per user tile, so no more
   // splits than that takes
-  int64_t s = (tk_cus() + ut - 1) / ut;
+  int64_t s = (device_cus() + ut - 1) / ut;
   if (s > it) s = it;
   if (s > TK_MAX_SPLITS) s = TK_MAX_SPLITS;
   return static_cast<int32_t>(s < 1 ? 1 : s);

@@ -8,27 +8,17 @@
 #include <algorithm>
 
 #include "common.h"
+#include "frag.h"
 
 namespace mrec {
 
 // ---------------------------------------------------------------------------
-// pairwise losses
+// pairwise losses (sigmoid_stable, dsigmoid_stable: frag.h)
 // ---------------------------------------------------------------------------
-// sigmoid(x) and sigmoid'(x) = s (1 - s) from e = exp(-|x|): no cancellation in 1 - s
-__device__ __forceinline__ float sigmoid_f(float x) {
-  const float e = expf(-fabsf(x));
-  return (x >= 0.f ? 1.f : e) / (1.f + e);
-}
-__device__ __forceinline__ float dsigmoid_f(float x) {
-  const float e = expf(-fabsf(x));
-  const float d = 1.f + e;
-  return e / (d * d);
-}
-
 __device__ __forceinline__ float pair_loss(int kind, float pos, float neg) {
   const float x = neg - pos;
   if (kind == MREC_PAIR_BPR) return x > 20.f ? x : log1pf(expf(x));  // torch's softplus
-  return sigmoid_f(x) + sigmoid_f(neg * neg);
+  return sigmoid_stable(x) + sigmoid_stable(neg * neg);
 }
 
 // dl/dpos, dl/dneg
@@ -36,13 +26,13 @@ __device__ __forceinline__ void pair_grad(int kind, float pos, float neg, float 
                                           float &dneg) {
   const float x = neg - pos;
   if (kind == MREC_PAIR_BPR) {
-    const float s = x > 20.f ? 1.f : sigmoid_f(x);  // softplus' under torch's threshold
+    const float s = x > 20.f ? 1.f : sigmoid_stable(x);  // softplus' under torch's threshold
     dpos = -s;
     dneg = s;
   } else {
-    const float d = dsigmoid_f(x);
+    const float d = dsigmoid_stable(x);
     dpos = -d;
-    dneg = d + 2.f * neg * dsigmoid_f(neg * neg);
+    dneg = d + 2.f * neg * dsigmoid_stable(neg * neg);
   }
 }
 

@@ -40,12 +40,9 @@
 // LDS: 12 bf16 tiles (X Q K P C F + two gradient tiles + four weights) 108 KiB, three
 // fp32 [64][64] buffers 48 KiB, vectors 2 KiB: 158 KiB, one workgroup per CU.
 #include "common.h"
+#include "frag.h"
 
 namespace mrec {
-
-typedef short sr_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float sr_f32x4 __attribute__((ext_vector_type(4)));
-typedef short sr_i16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SR_ROWS = 64;  // history positions per sample, padded
 constexpr int SR_THREADS = 512;
@@ -123,28 +120,17 @@ __device__ __forceinline__ SrLds sr_lds(char *base) {
 // operand fragment of rows r0 .. r0 + 15, k0 .. k0 + 31: element (r, k) is
 // base[r][k], or base[k][r] with TR (the tile holds the operand transposed)
 template <bool TR>
-__device__ __forceinline__ sr_bf16x8 sr_frag(const uint16_t *base, int r0, int k0, int lane) {
+__device__ __forceinline__ bf16x8 sr_frag(const uint16_t *base, int r0, int k0, int lane) {
   const int r = r0 + (lane & 15), k = k0 + 8 * (lane >> 4);
   if constexpr (!TR) {
-    return *reinterpret_cast<const sr_bf16x8 *>(base + r * SR_LD + k);
+    return *reinterpret_cast<const bf16x8 *>(base + r * SR_LD + k);
   } else {
-    // ds_read_b64_tr_b16: per 16-lane group a block of 4 tile rows x 16 columns comes
-    // back column-major: lane 4 q + p of the group addresses row q, columns 4 p .. + 3,
-    // lane i receives column i of the four rows.  Two blocks (rows k .. + 3, k + 4 .. + 7)
-    // are the lane's 8 k values.  Every lane of the wave takes part (callers branch per
-    // wave only) and every address lies inside the tile.
+    // two transposing reads (frag.h): tile rows k .. + 3 and k + 4 .. + 7 are the lane's
+    // 8 k values; every address lies inside the tile
     const int li = lane & 15;
     const uint16_t *p = base + (k + (li >> 2)) * SR_LD + r0 + 4 * (li & 3);
-    const sr_i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) sr_i16x4 *)(p));
-    const sr_i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) sr_i16x4 *)(p + 4 * SR_LD));
-    return sr_bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return lds_tr16_pair(p, 4 * SR_LD);
   }
-}
-
-__device__ __forceinline__ sr_f32x4 sr_mfma(sr_bf16x8 a, sr_bf16x8 b, sr_f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
 // An [16 MT, 16 NT] product's tiles t = wave, wave + 8, ... (tile t: rows 16 (t / NT),
@@ -152,10 +138,10 @@ __device__ __forceinline__ sr_f32x4 sr_mfma(sr_bf16x8 a, sr_bf16x8 b, sr_f32x4 c
 template <int MT, int NT>
 struct SrAcc {
   static constexpr int N = (MT * NT + SR_WAVES - 1) / SR_WAVES;
-  sr_f32x4 a[N];
+  f32x4 a[N];
   __device__ __forceinline__ void zero() {
 #pragma unroll
-    for (int i = 0; i < N; ++i) a[i] = sr_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < N; ++i) a[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 };
 
@@ -169,8 +155,8 @@ __device__ __forceinline__ void sr_mma(const uint16_t *A, const uint16_t *B, int
       const int mt = t / NT, nt = t % NT;
 #pragma unroll
       for (int s = 0; s < KS; ++s)
-        acc.a[i] = sr_mfma(sr_frag<TA>(A, 16 * mt, 32 * s, lane),
-                           sr_frag<TB>(B, 16 * nt, 32 * s, lane), acc.a[i]);
+        acc.a[i] = mfma_16x16x32(sr_frag<TA>(A, 16 * mt, 32 * s, lane),
+                                 sr_frag<TB>(B, 16 * nt, 32 * s, lane), acc.a[i]);
     }
   }
 }
@@ -653,19 +639,6 @@ using namespace mrec;
 
 namespace {
 
-int sr_cus() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        v <= 0)
-      v = 256;
-    (void)hipGetLastError();
-    return v;
-  }();
-  return n;
-}
-
 template <int D>
 void sr_set_attrs() {
   for (const void *k : {reinterpret_cast<const void *>(sasrec_fwd_kernel<D>),
@@ -729,7 +702,7 @@ int32_t mrec_sasrec_supported(int32_t D, int32_t L) {
 }
 
 int64_t mrec_sasrec_parts(int64_t batch) {
-  const int64_t g = sr_cus();
+  const int64_t g = device_cus();
   return batch < g ? (batch > 0 ? batch : 1) : g;
 }
 

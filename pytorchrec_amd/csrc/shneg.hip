@@ -34,11 +34,9 @@
 #include <algorithm>
 
 #include "common.h"
+#include "frag.h"
 
 namespace mrec {
-
-typedef short sh_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float sh_f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int SH_T = 32;            // held rows per workgroup
 constexpr int SH_W = 4;             // waves per workgroup
@@ -49,20 +47,8 @@ constexpr int SH_MAX_SPLITS = 64;
 constexpr int SH_TLD = 36;          // row pitch of the transposed image (bf16 elements, 8-B rows)
 constexpr int SH_RT = 1024;         // threads of the loss reduction
 
-struct ShMat {
-  const char *p;
-  int64_t ld_bytes;
-  int32_t bf16;
-};
-
-struct ShOut {
-  char *p;
-  int64_t ld_bytes;
-  int32_t bf16;
-};
-
 struct ShArgs {
-  ShMat q, pos, neg;
+  MatIn q, pos, neg;
   int64_t B, S;
   const void *pos_id, *neg_id;
   int32_t id64;
@@ -71,52 +57,10 @@ struct ShArgs {
   float *stats;   // [B][4]: s+, maximum, sum (softmax), n_b
   float *loss_b;  // [B]
   const float *g;
-  ShOut dq, dpos, dneg;
+  MatOut dq, dpos, dneg;
   float *ws;  // candidate-major partials [chunks][S][D], splits > 1 only
   int32_t splits, chunks_per_split;
 };
-
-__device__ __forceinline__ float sh_sigmoid(float x) {
-  const float e = expf(-fabsf(x));
-  return (x >= 0.f ? 1.f : e) / (1.f + e);
-}
-__device__ __forceinline__ float sh_dsigmoid(float x) {
-  const float e = expf(-fabsf(x));
-  const float d = 1.f + e;
-  return e / (d * d);
-}
-
-__device__ __forceinline__ sh_bf16x8 sh_zero8() {
-  return __builtin_bit_cast(sh_bf16x8, make_uint4(0, 0, 0, 0));
-}
-
-// elements [col0, col0 + 8) of row `row` as one MFMA fragment (an fp32 row is rounded here)
-__device__ __forceinline__ sh_bf16x8 sh_load8(const ShMat &m, int64_t row, int col0) {
-  const char *rp = m.p + row * m.ld_bytes;
-  if (m.bf16) return __builtin_bit_cast(sh_bf16x8, *reinterpret_cast<const uint4 *>(rp + 2 * col0));
-  const uint4 a = *reinterpret_cast<const uint4 *>(rp + 4 * col0);
-  const uint4 b = *reinterpret_cast<const uint4 *>(rp + 4 * col0 + 16);
-  return __builtin_bit_cast(
-      sh_bf16x8, make_uint4(pack_bf16x2(__uint_as_float(a.x), __uint_as_float(a.y)),
-                            pack_bf16x2(__uint_as_float(a.z), __uint_as_float(a.w)),
-                            pack_bf16x2(__uint_as_float(b.x), __uint_as_float(b.y)),
-                            pack_bf16x2(__uint_as_float(b.z), __uint_as_float(b.w))));
-}
-
-// one element as the bf16 value the products use
-__device__ __forceinline__ float sh_elem(const ShMat &m, int64_t row, int col) {
-  const char *rp = m.p + row * m.ld_bytes;
-  if (m.bf16) return bf16_to_f32(reinterpret_cast<const uint16_t *>(rp)[col]);
-  return bf16_to_f32(f32_to_bf16_rne(reinterpret_cast<const float *>(rp)[col]));
-}
-
-__device__ __forceinline__ void sh_store(const ShOut &o, int64_t row, int col, float v) {
-  char *rp = o.p + row * o.ld_bytes;
-  if (o.bf16)
-    reinterpret_cast<uint16_t *>(rp)[col] = f32_to_bf16_rne(v);
-  else
-    reinterpret_cast<float *>(rp)[col] = v;
-}
 
 __device__ __forceinline__ long long sh_id(const void *ids, int id64, int64_t i) {
   return id64 ? static_cast<long long>(static_cast<const int64_t *>(ids)[i])
@@ -146,12 +90,12 @@ __device__ __forceinline__ float sh_coef(int kind, float s, float sp, float mx, 
   }
   const float x = s - sp;
   if (kind == MREC_SHNEG_BPR) {
-    pp = (x > 20.f ? 1.f : sh_sigmoid(x)) * c;  // softplus' under torch's threshold
+    pp = (x > 20.f ? 1.f : sigmoid_stable(x)) * c;  // softplus' under torch's threshold
     return pp;
   }
-  const float d = sh_dsigmoid(x);
+  const float d = dsigmoid_stable(x);
   pp = d * c;
-  return (d + 2.f * s * sh_dsigmoid(s * s)) * c;
+  return (d + 2.f * s * dsigmoid_stable(s * s)) * c;
 }
 
 // ---------------------------------------------------------------------------
@@ -181,14 +125,14 @@ __global__ __launch_bounds__(SH_THREADS) void shneg_fwd_kernel(ShArgs p) {
 #pragma unroll
       for (int k = 0; k < D / 8; ++k) {
         const int d = part * (D / 8) + k;
-        s = fmaf(sh_elem(p.q, q0 + qi, d), sh_elem(p.pos, q0 + qi, d), s);
+        s = fmaf(mat_elem_bf16(p.q, q0 + qi, d), mat_elem_bf16(p.pos, q0 + qi, d), s);
       }
     }
     spart[qi][part] = s;
   }
-  sh_bf16x8 qf[KS];
+  bf16x8 qf[KS];
 #pragma unroll
-  for (int s = 0; s < KS; ++s) qf[s] = qlive && klive ? sh_load8(p.q, qrow, 16 * s + 8 * h) : sh_zero8();
+  for (int s = 0; s < KS; ++s) qf[s] = qlive && klive ? mat_load8(p.q, qrow, 16 * s + 8 * h) : frag_zero8();
   const long long qid = has_id && qlive ? sh_id(p.pos_id, p.id64, qrow) : 0;
   __syncthreads();
   float sp = 0.f;
@@ -206,13 +150,13 @@ __global__ __launch_bounds__(SH_THREADS) void shneg_fwd_kernel(ShArgs p) {
       row_bias[wave][r] = rlive && p.neg_bias ? p.neg_bias[row0 + r] : 0.f;
       row_id[wave][r] = rlive && has_id ? sh_id(p.neg_id, p.id64, row0 + r) : 0;
     }
-    sh_f32x16 acc;
+    f32x16 acc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0.f;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
-      const sh_bf16x8 af = rlive && klive ? sh_load8(p.neg, row0 + r, 16 * s + 8 * h) : sh_zero8();
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, qf[s], acc, 0, 0, 0);
+      const bf16x8 af = rlive && klive ? mat_load8(p.neg, row0 + r, 16 * s + 8 * h) : frag_zero8();
+      acc = mfma_32x32x16(af, qf[s], acc);
     }
     __syncthreads();
     float sc[16];
@@ -246,7 +190,7 @@ __global__ __launch_bounds__(SH_THREADS) void shneg_fwd_kernel(ShArgs p) {
     } else {
 #pragma unroll
       for (int e = 0; e < 16; ++e)
-        if (ok[e]) l += sh_sigmoid(sc[e] - sp) + sh_sigmoid(sc[e] * sc[e]);
+        if (ok[e]) l += sigmoid_stable(sc[e] - sp) + sigmoid_stable(sc[e] * sc[e]);
     }
     __syncthreads();
   }
@@ -319,8 +263,8 @@ __global__ __launch_bounds__(SH_THREADS) void shneg_bwd_kernel(ShArgs p) {
   __shared__ float psum_s[SH_W * 2][SH_T];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
-  const ShMat &held = QM ? p.q : p.neg;
-  const ShMat &strm = QM ? p.neg : p.q;
+  const MatIn &held = QM ? p.q : p.neg;
+  const MatIn &strm = QM ? p.neg : p.q;
   const int64_t NH = QM ? p.B : p.S, NS = QM ? p.S : p.B;
   const int64_t h0 = static_cast<int64_t>(blockIdx.x) * SH_T;
   const int64_t hrow = h0 + r;
@@ -328,9 +272,9 @@ __global__ __launch_bounds__(SH_THREADS) void shneg_bwd_kernel(ShArgs p) {
   const bool klive = 8 * h < D;
   const bool has_id = p.pos_id != nullptr;
 
-  sh_bf16x8 hf[KS];
+  bf16x8 hf[KS];
 #pragma unroll
-  for (int s = 0; s < KS; ++s) hf[s] = hlive && klive ? sh_load8(held, hrow, 16 * s + 8 * h) : sh_zero8();
+  for (int s = 0; s < KS; ++s) hf[s] = hlive && klive ? mat_load8(held, hrow, 16 * s + 8 * h) : frag_zero8();
   long long hid = 0;
   float h_sp = 0.f, h_mx = 0.f, h_c = 0.f, h_bias = 0.f;
   if (hlive) {
@@ -356,7 +300,7 @@ __global__ __launch_bounds__(SH_THREADS) void shneg_bwd_kernel(ShArgs p) {
   float psum = 0.f;
 
   for (int64_t chunk = c0; chunk < c1; ++chunk) {
-    sh_f32x16 Z[NCB];
+    f32x16 Z[NCB];
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
@@ -381,14 +325,14 @@ __global__ __launch_bounds__(SH_THREADS) void shneg_bwd_kernel(ShArgs p) {
         row_par[wave][r] = par;
         row_id[wave][r] = id;
       }
-      sh_bf16x8 af[KS];
-      sh_f32x16 acc;
+      bf16x8 af[KS];
+      f32x16 acc;
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[e] = 0.f;
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
-        af[s] = rlive && klive ? sh_load8(strm, row0 + r, 16 * s + 8 * h) : sh_zero8();
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s], hf[s], acc, 0, 0, 0);
+        af[s] = rlive && klive ? mat_load8(strm, row0 + r, 16 * s + 8 * h) : frag_zero8();
+        acc = mfma_32x32x16(af[s], hf[s], acc);
       }
       __syncthreads();
       // the coefficients of this lane's held row against its 16 streamed rows
@@ -433,8 +377,8 @@ __global__ __launch_bounds__(SH_THREADS) void shneg_bwd_kernel(ShArgs p) {
           ch[k] = pack_bf16x2(w0, w1);
           cl[k] = pack_bf16x2(w0 - __uint_as_float(ch[k] << 16), w1 - __uint_as_float(ch[k] & 0xffff0000u));
         }
-        const sh_bf16x8 cf_hi = __builtin_bit_cast(sh_bf16x8, make_uint4(ch[0], ch[1], ch[2], ch[3]));
-        const sh_bf16x8 cf_lo = __builtin_bit_cast(sh_bf16x8, make_uint4(cl[0], cl[1], cl[2], cl[3]));
+        const bf16x8 cf_hi = __builtin_bit_cast(bf16x8, make_uint4(ch[0], ch[1], ch[2], ch[3]));
+        const bf16x8 cf_lo = __builtin_bit_cast(bf16x8, make_uint4(cl[0], cl[1], cl[2], cl[3]));
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) {
           const int d = 32 * cb + r;
@@ -443,9 +387,9 @@ __global__ __launch_bounds__(SH_THREADS) void shneg_bwd_kernel(ShArgs p) {
             lo = *reinterpret_cast<const uint2 *>(&timg[wave][d][16 * s2 + 4 * h]);
             hi = *reinterpret_cast<const uint2 *>(&timg[wave][d][16 * s2 + 8 + 4 * h]);
           }
-          const sh_bf16x8 bf = __builtin_bit_cast(sh_bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
-          Z[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cf_hi, bf, Z[cb], 0, 0, 0);
-          Z[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cf_lo, bf, Z[cb], 0, 0, 0);
+          const bf16x8 bf = __builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
+          Z[cb] = mfma_32x32x16(cf_hi, bf, Z[cb]);
+          Z[cb] = mfma_32x32x16(cf_lo, bf, Z[cb]);
         }
       }
     }
@@ -490,28 +434,28 @@ __global__ __launch_bounds__(SH_THREADS) void shneg_bwd_kernel(ShArgs p) {
         for (int k = 0; k < 2 * SH_W; ++k) s += psum_s[k][row];
         ap = -s;
       }
-      const float pv = ap == 0.f ? 0.f : ap * sh_elem(p.pos, h0 + row, d);
-      const float qv = ap == 0.f ? 0.f : ap * sh_elem(p.q, h0 + row, d);
-      sh_store(p.dq, h0 + row, d, tot[i] + pv);
-      sh_store(p.dpos, h0 + row, d, qv);
+      const float pv = ap == 0.f ? 0.f : ap * mat_elem_bf16(p.pos, h0 + row, d);
+      const float qv = ap == 0.f ? 0.f : ap * mat_elem_bf16(p.q, h0 + row, d);
+      mat_store(p.dq, h0 + row, d, tot[i] + pv);
+      mat_store(p.dpos, h0 + row, d, qv);
     }
   } else if (p.splits == 1) {
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
       const int e = tid + SH_THREADS * i;
-      if (h0 + e / D < NH) sh_store(p.dneg, h0 + e / D, e % D, tot[i]);
+      if (h0 + e / D < NH) mat_store(p.dneg, h0 + e / D, e % D, tot[i]);
     }
   }
 }
 
 // dneg from the per-chunk partials, in chunk order (the order a single split sums them in)
 __global__ __launch_bounds__(256) void shneg_ws_reduce_kernel(const float *__restrict__ ws, int64_t S, int D,
-                                                              int64_t n_chunks, ShOut dneg) {
+                                                              int64_t n_chunks, MatOut dneg) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
   if (i >= S * D) return;
   float tot = 0.f;
   for (int64_t c = 0; c < n_chunks; ++c) tot += ws[c * S * D + i];
-  sh_store(dneg, i / D, static_cast<int>(i % D), tot);
+  mat_store(dneg, i / D, static_cast<int>(i % D), tot);
 }
 
 // the device functions the losses call, one per element (the tolerance probe of the tests)
@@ -525,8 +469,8 @@ __global__ __launch_bounds__(256) void shneg_math_kernel(int fn, const float *__
     case 0: o = expf(v); break;
     case 1: o = logf(v); break;
     case 2: o = v > 20.f ? v : log1pf(expf(v)); break;
-    case 3: o = sh_sigmoid(v); break;
-    default: o = sh_dsigmoid(v); break;
+    case 3: o = sigmoid_stable(v); break;
+    default: o = dsigmoid_stable(v); break;
   }
   y[i] = o;
 }
@@ -538,27 +482,10 @@ using namespace mrec;
 namespace {
 
 bool sh_dim_ok(int32_t D) { return D == 8 || D == 16 || D == 32 || D == 64; }
-bool sh_fdt(mrec_dtype t) { return t == MREC_F32 || t == MREC_BF16; }
-
-int sh_cus() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      v = 256;
-    (void)hipGetLastError();
-    return v;
-  }();
-  return n;
-}
 
 int64_t sh_chunks(int64_t batch) { return (batch + SH_CHUNK - 1) / SH_CHUNK; }
 
-// a [rows, D] operand: 16-byte aligned rows the fragment loads can take
-bool sh_mat_ok(const void *p, int64_t ld, int32_t D, mrec_dtype t) {
-  const int64_t eb = t == MREC_F32 ? 4 : 2;
-  return p && ld >= D && (ld * eb) % 16 == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0;
-}
+// an output: rows of at least D elements, element aligned (weaker than rows16_ok)
 bool sh_out_ok(const void *p, int64_t ld, int32_t D, mrec_dtype t) {
   const uintptr_t eb = t == MREC_F32 ? 4 : 2;
   return p && ld >= D && (reinterpret_cast<uintptr_t>(p) & (eb - 1)) == 0;
@@ -579,9 +506,9 @@ mrec_status sh_check(const mrec_shneg_args *a, bool bwd, ShArgs &p) {
   MREC_CHECK_ARG(!a->pos_id || a->id_dtype == MREC_I32 || a->id_dtype == MREC_I64, "ids must be int32 or int64");
   MREC_CHECK_ARG(a->splits >= 0 && a->splits <= SH_MAX_SPLITS, "splits must be in 0 .. 64 (0: the default)");
   if (a->batch > 0) {
-    MREC_CHECK_ARG(sh_mat_ok(a->q, a->ldq, a->D, a->q_dtype) && sh_mat_ok(a->pos, a->ld_pos, a->D, a->row_dtype),
+    MREC_CHECK_ARG(rows16_ok(a->q, a->ldq, a->D, a->q_dtype) && rows16_ok(a->pos, a->ld_pos, a->D, a->row_dtype),
                    "q and pos need 16-byte aligned rows of at least D elements");
-    MREC_CHECK_ARG(a->n_neg == 0 || sh_mat_ok(a->neg, a->ld_neg, a->D, a->row_dtype),
+    MREC_CHECK_ARG(a->n_neg == 0 || rows16_ok(a->neg, a->ld_neg, a->D, a->row_dtype),
                    "neg needs 16-byte aligned rows of at least D elements");
     MREC_CHECK_ARG(a->stats != nullptr, "NULL stats");
     if (!bwd) {
@@ -605,10 +532,9 @@ mrec_status sh_check(const mrec_shneg_args *a, bool bwd, ShArgs &p) {
     }
     p.splits = splits;
   }
-  const int64_t qb = a->q_dtype == MREC_F32 ? 4 : 2, rb = a->row_dtype == MREC_F32 ? 4 : 2;
-  p.q = ShMat{static_cast<const char *>(a->q), a->ldq * qb, a->q_dtype == MREC_BF16};
-  p.pos = ShMat{static_cast<const char *>(a->pos), a->ld_pos * rb, a->row_dtype == MREC_BF16};
-  p.neg = ShMat{static_cast<const char *>(a->neg), a->ld_neg * rb, a->row_dtype == MREC_BF16};
+  p.q = mat_in(a->q, a->ldq, a->q_dtype);
+  p.pos = mat_in(a->pos, a->ld_pos, a->row_dtype);
+  p.neg = mat_in(a->neg, a->ld_neg, a->row_dtype);
   p.B = a->batch;
   p.S = a->n_neg;
   p.pos_id = a->pos_id;
@@ -620,9 +546,9 @@ mrec_status sh_check(const mrec_shneg_args *a, bool bwd, ShArgs &p) {
   p.reduction = a->reduction;
   p.stats = a->stats;
   p.g = a->g;
-  p.dq = ShOut{static_cast<char *>(a->dq), a->ld_dq * qb, a->q_dtype == MREC_BF16};
-  p.dpos = ShOut{static_cast<char *>(a->dpos), a->ld_dpos * rb, a->row_dtype == MREC_BF16};
-  p.dneg = ShOut{static_cast<char *>(a->dneg), a->ld_dneg * rb, a->row_dtype == MREC_BF16};
+  p.dq = mat_out(a->dq, a->ld_dq, a->q_dtype);
+  p.dpos = mat_out(a->dpos, a->ld_dpos, a->row_dtype);
+  p.dneg = mat_out(a->dneg, a->ld_dneg, a->row_dtype);
   p.ws = static_cast<float *>(a->workspace);
   return MREC_OK;
 }
@@ -651,7 +577,7 @@ void sh_launch_dim(int D, const ShArgs &p, int pass, dim3 grid, hipStream_t s) {
 extern "C" {
 
 int32_t mrec_shneg_supported(int32_t D, mrec_dtype q_dtype, mrec_dtype row_dtype) {
-  return sh_dim_ok(D) && sh_fdt(q_dtype) && sh_fdt(row_dtype);
+  return sh_dim_ok(D) && is_float_dtype(q_dtype) && is_float_dtype(row_dtype);
 }
 
 int32_t mrec_shneg_tile_queries(void) { return SH_T; }
@@ -661,7 +587,7 @@ int32_t mrec_shneg_splits(int64_t batch, int64_t n_neg) {
   if (batch <= 0 || n_neg <= 0) return 1;
   const int64_t ct = (n_neg + SH_T - 1) / SH_T;
   // fill the CUs twice over when the pool is small; whole chunks of the batch only
-  int64_t s = (2 * sh_cus() + ct - 1) / ct;
+  int64_t s = (2 * device_cus() + ct - 1) / ct;
   s = std::min<int64_t>(s, sh_chunks(batch));
   s = std::min<int64_t>(s, SH_MAX_SPLITS);
   return static_cast<int32_t>(s < 1 ? 1 : s);

@@ -21,12 +21,10 @@
 // (a tile can add TK_TI keys to a query at the most) every buffer is sorted, cut to k, and
 // the thresholds are raised.  The result is a function of the inputs alone.
 #include "common.h"
+#include "frag.h"
 #include "topk_select.h"
 
 namespace mrec {
-
-typedef short tk_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float tk_f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int TK_TQ = 32;        // queries per workgroup
 constexpr int TK_TI = 128;       // items per streamed tile: 32 per wave
@@ -50,23 +48,6 @@ struct TopkArgs {
   TkOut o;
 };
 
-// One K-step's A fragment of this lane from the raw 16-byte loads of its 8 elements (one
-// load of a bf16 row, two of an fp32 row: rounded here, at use, so that a fetched tile
-// waits for nothing until its products).
-template <typename T>
-__device__ __forceinline__ tk_bf16x8 tk_frag(const uint4 *raw, int s) {
-  if constexpr (sizeof(T) == 2) {
-    return __builtin_bit_cast(tk_bf16x8, raw[s]);
-  } else {
-    const uint4 a = raw[2 * s], b = raw[2 * s + 1];
-    return __builtin_bit_cast(
-        tk_bf16x8, make_uint4(pack_bf16x2(__uint_as_float(a.x), __uint_as_float(a.y)),
-                              pack_bf16x2(__uint_as_float(a.z), __uint_as_float(a.w)),
-                              pack_bf16x2(__uint_as_float(b.x), __uint_as_float(b.y)),
-                              pack_bf16x2(__uint_as_float(b.z), __uint_as_float(b.w))));
-  }
-}
-
 // D: the embedding size (8 is one zero-padded K-step); T: the bank's element type
 template <int D, typename T>
 __global__ __launch_bounds__(TK_THREADS) void topk_scan_kernel(TopkArgs p) {
@@ -83,7 +64,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_scan_kernel(TopkArgs p) {
   if (tid < TK_TQ) cnt[tid] = 0, thr[tid] = 0;
 
   // the query tile as B fragments: element j of K-step s is q[qrow][16 s + 8 h + j]
-  tk_bf16x8 qf[KS];
+  bf16x8 qf[KS];
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
     float f[8];
@@ -96,8 +77,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_scan_kernel(TopkArgs p) {
                         : static_cast<const float *>(p.q)[e];
       }
     }
-    qf[s] = __builtin_bit_cast(tk_bf16x8, make_uint4(pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]),
-                                                     pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7])));
+    qf[s] = frag_pack8(f);
   }
   // the query's exclusion list [ex_lo, ex_hi)
   int64_t ex_lo = 0, ex_hi = 0;
@@ -114,7 +94,9 @@ __global__ __launch_bounds__(TK_THREADS) void topk_scan_kernel(TopkArgs p) {
   const int64_t t0 = static_cast<int64_t>(blockIdx.y) * p.tiles_per_split;
   const int64_t t1 = t0 + p.tiles_per_split < n_tiles ? t0 + p.tiles_per_split : n_tiles;
 
-  // raw 16-byte loads per lane and K-step, per tile; TK_PF tiles are in flight
+  // raw 16-byte loads per lane and K-step, per tile (one of a bf16 row, two of an fp32 row);
+  // TK_PF tiles are in flight, and frag_from_raw rounds an fp32 tile at use, so that a
+  // fetched tile waits for nothing until its products
   constexpr int LPS = sizeof(T) == 2 ? 1 : 2, RV = KS * LPS;
   auto fetch = [&](int64_t tile, uint4 (&raw)[RV]) {
     const int64_t item = p.low + tile * TK_TI + 32 * wave + r;
@@ -134,20 +116,20 @@ __global__ __launch_bounds__(TK_THREADS) void topk_scan_kernel(TopkArgs p) {
   for (int u = 0; u < TK_PF; ++u) fetch(t0 + u, st[u]);
   __syncthreads();
   for (int64_t tile = t0; tile < t1; ++tile) {
-    tk_bf16x8 af[KS];
+    bf16x8 af[KS];
 #pragma unroll
-    for (int s = 0; s < KS; ++s) af[s] = tk_frag<T>(st[0], s);
+    for (int s = 0; s < KS; ++s) af[s] = frag_from_raw<T>(st[0], s);
 #pragma unroll
     for (int u = 0; u + 1 < TK_PF; ++u) {
 #pragma unroll
       for (int i = 0; i < RV; ++i) st[u][i] = st[u + 1][i];
     }
     fetch(tile + TK_PF, st[TK_PF - 1]);
-    tk_f32x16 acc;
+    f32x16 acc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0.f;
 #pragma unroll
-    for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s], qf[s], acc, 0, 0, 0);
+    for (int s = 0; s < KS; ++s) acc = mfma_32x32x16(af[s], qf[s], acc);
     const int64_t item0 = p.low + tile * TK_TI + 32 * wave + 4 * h;  // + (e & 3) + 8 (e >> 2)
     if (p.w_off >= 0) {
 #pragma unroll
@@ -222,7 +204,7 @@ int32_t mrec_topk_splits(int64_t batch, int64_t n_items) {
   const int64_t qt = (batch + TK_TQ - 1) / TK_TQ, it = (n_items + TK_TI - 1) / TK_TI;
   // fill the CUs when the batch is small; the table is re-read once per query tile, so
   // no more splits than that takes
-  int64_t s = (tk_cus() + qt - 1) / qt;
+  int64_t s = (device_cus() + qt - 1) / qt;
   if (s > it) s = it;
   if (s > TK_MAX_SPLITS) s = TK_MAX_SPLITS;
   return static_cast<int32_t>(s < 1 ? 1 : s);

@@ -184,18 +184,6 @@ static __global__ __launch_bounds__(TK_THREADS) void topk_fill_kernel(TkOut o) {
   o.out_scores[b * o.ld_out + j] = -INFINITY;
 }
 
-inline int tk_cus() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      v = 256;
-    (void)hipGetLastError();
-    return v;
-  }();
-  return n;
-}
-
 inline int tk_pow2_at_least(int v) {
   int p = 2;
   while (p < v) p <<= 1;

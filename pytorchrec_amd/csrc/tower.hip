@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "frag.h"
 #include "tower_common.h"
 
 namespace mrec {
@@ -39,9 +40,6 @@ constexpr int TW_PF_DEFAULT = 8;         // k steps of weight fragments in fligh
 constexpr int TW_TPW = 4;                // output tiles per wave (<= 32 tiles = 512 wide)
 constexpr int TW_MAXNS = 64;             // side-linear width
 constexpr int TW_MAXC = 3;               // DCN-v2 cross layers ahead of the MLP (ABI 27)
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct TowerArgs {
   int64_t B;
@@ -102,9 +100,6 @@ struct TowerArgs {
   int p_cbias[TW_MAXC];
 };
 
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 // The MFMA main loop of one layer for a wave with NT real output tiles and G
 // groups of PF k steps (both compile-time: the loop is straight-line code, so the
 // compiler's vmcnt accounting keeps (PF - 1) * NT weight fragments in flight
@@ -141,7 +136,7 @@ __device__ __forceinline__ void tower_mfma_g(f32x4 (&acc)[TW_TPW], __amdgpu_buff
     const bf16x8 b = *reinterpret_cast<const bf16x8 *>(brow + tw_rot(s, rot, ksteps) * 64);
 #pragma unroll
     for (int i = 0; i < NT; ++i)
-      acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfr[p][i], b, acc[i], 0, 0, 0);
+      acc[i] = mfma_16x16x32(wfr[p][i], b, acc[i]);
     const int sn = s + TW_PF;
     if (sn < G * TW_PF) {  // compile-time
       const int so = sn < ksteps ? tw_rot(sn, rot, ksteps) * 1024 : img_bytes;
@@ -435,10 +430,7 @@ __device__ __forceinline__ void tower_store_kfrag(const char *blk, int s_blk, in
     const bool on = idx < n;
     const int t = on ? idx >> 5 : 0, gl = (idx >> 4) & 1;
     const char *q = blk + (8 * gl + (i16 >> 2)) * s_blk + (t * 16 + 4 * (i16 & 3)) * 2;
-    typedef short v4s_t __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) v4s_t lds_v4s_t;
-    const v4s_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t *)(q));
-    const v4s_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t *)(q + 4 * s_blk));
+    const bf16x4 lo = lds_tr16_b64(q), hi = lds_tr16_b64(q + 4 * s_blk);
     if (!on) continue;
     uint32_t w[4] = {static_cast<uint16_t>(lo[0]) | (uint32_t(static_cast<uint16_t>(lo[1])) << 16),
                      static_cast<uint16_t>(lo[2]) | (uint32_t(static_cast<uint16_t>(lo[3])) << 16),

@@ -27,6 +27,7 @@
 
 #include "common.h"
 #include "feed_common.h"
+#include "frag.h"
 #include "head_common.h"
 #include "tower_common.h"
 
@@ -39,9 +40,6 @@ constexpr int DW_PF = MREC_DW_PF;  // k steps of fragments in flight per wave
 constexpr int DW_MAXL = 8;
 constexpr int DW_TILE = 64;    // output tile edge of one wave (4 MFMA tiles)
 constexpr int DW_OOB = 1 << 30;  // a voffset past every image: the load returns zeros
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct DwLayer {
   const uint16_t *dy;  // k-fragment image of dY [B, n_out]
@@ -153,7 +151,7 @@ __global__ __launch_bounds__(64) void tower_dw_kernel(DwArgs a, KClock kc) {
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[p][i], bj[j], acc[i][j], 0, 0, 0);
+          acc[i][j] = mfma_16x16x32(fa[p][i], bj[j], acc[i][j]);
       load(p, base + p + PF);
       __builtin_amdgcn_sched_barrier(0);
     }

@@ -972,6 +972,32 @@ def _sasrec_params(model):
             model.W1.bias, model.W2.weight, model.W2.bias, ln.weight, ln.bias)
 
 
+def _sum_partials(bwd_name, a, rows, parts, P, sizes, params, dev, order=None):
+    """The tail the fused encoders' backwards share.  ``bwd_name`` (argument block ``a``,
+    launched when there are ``rows``) leaves per-workgroup partials [parts, P] of the dense
+    gradients; mrec_sasrec_wgrad, which is shape-agnostic, sums them in workgroup order.
+    The sum is split by ``sizes`` and piece ``order[i]`` (piece i without ``order``) is
+    parameter i's gradient.  -> the gradients of ``params``; under data parallelism they
+    go into the flat buffer IModel all-reduces instead and every entry is None."""
+    part = torch.empty(parts, P, dtype=torch.float32, device=dev)
+    g = torch.zeros(P, dtype=torch.float32, device=dev)
+    a.part, a.parts = part.data_ptr(), parts
+    st = _mrec.stream_handle()
+    if rows:
+        _mrec.call(bwd_name, ctypes.byref(a), st)
+        _mrec.call("mrec_sasrec_wgrad", part.data_ptr(), parts, P, g.data_ptr(), st)
+    pieces = torch.split(g, sizes)
+    if order is not None:
+        pieces = [pieces[i] for i in order]
+    grads = [t.view_as(p) for t, p in zip(pieces, params)]
+    dpg = dp_grads(*params)
+    if dpg is None:
+        return tuple(grads)
+    for dst, src in zip(dpg, grads):
+        dst.copy_(src.view_as(dst))
+    return (None,) * len(params)
+
+
 class _SasrecFn(torch.autograd.Function):
     """The whole SASRec encoder over the gathered history rows [B, L, D]: one forward
     launch (every layer -> v [B, D], the layer outputs saved), one backward launch
@@ -1017,29 +1043,15 @@ class _SasrecFn(torch.autograd.Function):
         dev = rows2.device
         dv = dv.detach().float().contiguous()
         d_rows = torch.empty(B * L, D, dtype=_BF16, device=dev)
-        lib = _mrec.lib()
-        parts = int(lib.mrec_sasrec_parts(B))
-        P = int(lib.mrec_sasrec_param_count(D, ws[0].shape[0]))
-        part = torch.empty(parts, P, dtype=torch.float32, device=dev)
-        g = torch.zeros(P, dtype=torch.float32, device=dev)
         a.dv, a.d_rows, a.ld_drows = dv.data_ptr(), d_rows.data_ptr(), d_rows.stride(0)
-        a.part, a.parts = part.data_ptr(), parts
-        st = _mrec.stream_handle()
-        if B:
-            _mrec.call("mrec_sasrec_bwd", ctypes.byref(a), st)
-            _mrec.call("mrec_sasrec_wgrad", part.data_ptr(), parts, P, g.data_ptr(), st)
-        ctx.args = ctx.keep = None
+        lib = _mrec.lib()
+        # the kernel's partial: [wq, wk, w1, w2, b1, b2, gamma, beta, pos]
         sizes = [D * D] * 4 + [D] * 4 + [ws[0].shape[0] * D]
-        gq, gk, g1, g2, gb1, gb2, gga, gbe, gpos = torch.split(g, sizes)
-        grads = [t.view_as(p) for t, p in
-                 zip((gpos, gq, gk, g1, gb1, g2, gb2, gga, gbe), params)]
-        head = (d_rows.reshape(B, L, D), None, None, None, None, None)
-        dpg = dp_grads(*params)
-        if dpg is not None:  # data parallel: into the flat buffer IModel all-reduces
-            for dst, src in zip(dpg, grads):
-                dst.copy_(src.view_as(dst))
-            return head + (None,) * 9
-        return head + tuple(grads)
+        grads = _sum_partials("mrec_sasrec_bwd", a, B, int(lib.mrec_sasrec_parts(B)),
+                              int(lib.mrec_sasrec_param_count(D, ws[0].shape[0])), sizes,
+                              params, dev, order=(8, 0, 1, 2, 4, 3, 5, 6, 7))
+        ctx.args = ctx.keep = None
+        return (d_rows.reshape(B, L, D), None, None, None, None, None) + grads
 
 
 def sasrec_encode(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor,
@@ -1120,27 +1132,13 @@ class _GruFn(torch.autograd.Function):
         dev = rows2.device
         dh = dh.detach().float().contiguous()
         d_rows = torch.empty(B * L, E, dtype=_BF16, device=dev)
-        lib = _mrec.lib()
-        parts = int(lib.mrec_gru_parts(B))
-        P = int(lib.mrec_gru_param_count(E, H))
-        part = torch.empty(parts, P, dtype=torch.float32, device=dev)
-        g = torch.zeros(P, dtype=torch.float32, device=dev)
         a.dh_last, a.d_rows, a.ld_drows = dh.data_ptr(), d_rows.data_ptr(), d_rows.stride(0)
-        a.part, a.parts = part.data_ptr(), parts
-        st = _mrec.stream_handle()
-        if B:
-            _mrec.call("mrec_gru_bwd", ctypes.byref(a), st)
-            _mrec.call("mrec_sasrec_wgrad", part.data_ptr(), parts, P, g.data_ptr(), st)
+        lib = _mrec.lib()
+        grads = _sum_partials("mrec_gru_bwd", a, B, int(lib.mrec_gru_parts(B)),
+                              int(lib.mrec_gru_param_count(E, H)),
+                              [3 * H * E, 3 * H * H, 3 * H, 3 * H], params, dev)
         ctx.args = ctx.keep = None
-        grads = [t.view_as(p) for t, p in
-                 zip(torch.split(g, [3 * H * E, 3 * H * H, 3 * H, 3 * H]), params)]
-        head = (d_rows.reshape(B, L, E), None, None, None)
-        dpg = dp_grads(*params)
-        if dpg is not None:  # data parallel: into the flat buffer IModel all-reduces
-            for dst, src in zip(dpg, grads):
-                dst.copy_(src.view_as(dst))
-            return head + (None,) * 4
-        return head + tuple(grads)
+        return (d_rows.reshape(B, L, E), None, None, None) + grads
 
 
 def gru_encode(rows: torch.Tensor, his_len: torch.Tensor, model, order="auto") -> torch.Tensor:
@@ -1233,27 +1231,14 @@ class _NcfFn(torch.autograd.Function):
         dev = rows2.device
         dpred = dpred.detach().float().contiguous()
         d_rows = torch.empty(pairs, 4 * E, dtype=_BF16, device=dev)
-        lib = _mrec.lib()
-        parts = int(lib.mrec_ncf_parts(pairs))
-        P = int(lib.mrec_ncf_param_count(E, nl, a.widths))
-        part = torch.empty(parts, P, dtype=torch.float32, device=dev)
-        g = torch.zeros(P, dtype=torch.float32, device=dev)
         a.dpred, a.d_rows, a.ld_drows = dpred.data_ptr(), d_rows.data_ptr(), d_rows.stride(0)
-        a.part, a.parts = part.data_ptr(), parts
-        st = _mrec.stream_handle()
-        if pairs:
-            _mrec.call("mrec_ncf_bwd", ctypes.byref(a), st)
-            _mrec.call("mrec_sasrec_wgrad", part.data_ptr(), parts, P, g.data_ptr(), st)
-        ctx.args = ctx.keep = None
+        lib = _mrec.lib()
         sizes = [w.numel() for w in ws] + [b.numel() for b in bs] + [wp.numel()]
-        grads = [t.view_as(p) for t, p in zip(torch.split(g, sizes), params)]
-        head = (d_rows, None, None)
-        dpg = dp_grads(*params)
-        if dpg is not None:  # data parallel: into the flat buffer IModel all-reduces
-            for dst, src in zip(dpg, grads):
-                dst.copy_(src.view_as(dst))
-            return head + (None,) * len(params)
-        return head + tuple(grads)
+        grads = _sum_partials("mrec_ncf_bwd", a, pairs, int(lib.mrec_ncf_parts(pairs)),
+                              int(lib.mrec_ncf_param_count(E, nl, a.widths)), sizes,
+                              params, dev)
+        ctx.args = ctx.keep = None
+        return (d_rows, None, None) + grads
 
 
 def ncf_score(rows: torch.Tensor, model) -> torch.Tensor:
