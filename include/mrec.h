@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MREC_ABI_VERSION 38
+#define MREC_ABI_VERSION 39
 #define MREC_MAX_TABLES 64      /* tables per table bank / per call */
 #define MREC_BWD_MAX_BATCH 8192  /* lookups per table per plan/apply call */
 #define MREC_BWD_HASH_MAX_BATCH 4096  /* batches up to this use the hash plan */
@@ -1973,6 +1973,86 @@ int32_t mrec_dot_interact_supported(int32_t D, int32_t n_fields, mrec_dtype bot_
                                     mrec_dtype rows_dtype, mrec_dtype x_dtype, mrec_dtype dx_dtype);
 mrec_status mrec_dot_interact_fwd(const mrec_dot_interact_args *args, mrec_stream stream);
 mrec_status mrec_dot_interact_bwd(const mrec_dot_interact_args *args, mrec_stream stream);
+
+/* ------------------------------------------------------------------------- */
+/* CIN: xDeepFM's Compressed Interaction Network, one layer per call (ABI 39;  */
+/* csrc/cin.hip)                                                               */
+/* ------------------------------------------------------------------------- */
+/*
+ * With m = n_fields, X^0 = x0 read as [batch, m, D] (d fastest, row stride ld_x0) and
+ * X^{k-1} = xp read as [batch, H_prev, D] (row stride ld_xp; layer 1: xp = x0, H_prev = m):
+ *   X^k[b, h, d] = sum_{i < H_prev} sum_{j < m} W[h, i, j] * X^{k-1}[b, i, d] * X^0[b, j, d]
+ *   p[b, h]      = sum_d X^k[b, h, d]                       fp32, row stride ld_p
+ * Identity activation, no bias, every map feeds both p and the next layer.
+ *   Rounding.  x0, xp, W and dX^k enter the products as bf16 (RNE where stored in fp32; W
+ * through its images).  Z = bf16(xp * x0) is rounded once.  Accumulation is fp32 (MFMA).  p
+ * is summed from the fp32 accumulators; xk is rounded once when x_dtype is MREC_BF16.
+ *   Weight images (bf16, built by the caller whenever W changes; pad entries are zero):
+ *   w_fwd [mrec_cin_fwd_rows(H)][H_prev * MP]     w_fwd[h][i * MP + j] = W[h, i, j]
+ *   w_bwd [r32(H_prev * MP)][mrec_cin_bwd_cols(H)] w_bwd[i * MP + j][h] = W[h, i, j]
+ * MP = mrec_cin_field_pitch(n_fields) (16 or 32), r32 rounds up to a multiple of 32.
+ *   Backward (mrec_cin_bwd: one data-gradient launch and one weight-gradient launch).
+ * dX^k is dxk [batch, H, D] in x_dtype when given, else dp[b, h] broadcast over d (the last
+ * layer).  With g = bf16(dX^k):
+ *   dZ[b, (i, j), d]   = sum_h g[b, h, d] W[h, i, j]                    fp32, never stored
+ *   dxp[b, i, d]       = sum_j dZ X^0[b, j, d]  (+ dp_prev[b, i] when dp_prev is given)
+ *   dx0[b, j * D + d] += sum_i dZ X^{k-1}[b, i, d]                      fp32 accumulator
+ *   dw[h, i, j]        = sum_{b, d} g[b, h, d] * bf16(xp[b, i, d] * x0[b, j, d])
+ * dxp is rounded once into dxp_dtype.  dx0 is read and written by exactly one lane per
+ * element; the caller zeroes it before the first (topmost) layer's call.  For layer 1 xp is
+ * x0 and the caller adds dxp into dx0.  dw [H, H_prev, m] is contiguous fp32, overwritten.
+ *   Determinism: no atomics; xk, p, dxp and dx0 of a sample depend on that sample alone;
+ * dw is reduced over the batch in one fixed order by the one workgroup that owns the tile.
+ *   One description for both directions: the forward ignores the backward fields and w_bwd,
+ * the backward ignores xk, p and w_fwd.
+ * Compiled shapes (mrec_cin_supported): 2 <= n_fields <= 32, D in {8, 16, 32, 64}, H a
+ * multiple of 8 up to 256, H_prev the same or equal to n_fields; every dtype MREC_F32 or
+ * MREC_BF16.  x0, xp, xk, dxk, dxp and the images need 16-byte aligned rows.  batch = 0
+ * launches nothing.  Never read or written: columns past the stated widths, rows >= batch.
+ * Anything else is MREC_EINVAL with mrec_last_error() before any launch.
+ */
+typedef struct {
+  const void *x0;
+  mrec_dtype x0_dtype;
+  int64_t ld_x0;
+  const void *xp;
+  mrec_dtype xp_dtype;
+  int64_t ld_xp;
+  const void *w_fwd;
+  int64_t ld_w_fwd;
+  const void *w_bwd;
+  int64_t ld_w_bwd;
+  int64_t batch;
+  int32_t n_fields;
+  int32_t D;
+  int32_t H_prev;
+  int32_t H;
+  mrec_dtype x_dtype; /* of xk and dxk */
+  void *xk;
+  int64_t ld_xk;
+  float *p;
+  int64_t ld_p;
+  const void *dxk;
+  int64_t ld_dxk;
+  const float *dp;
+  int64_t ld_dp;
+  const float *dp_prev;
+  int64_t ld_dp_prev;
+  void *dxp;
+  mrec_dtype dxp_dtype;
+  int64_t ld_dxp;
+  float *dx0;
+  int64_t ld_dx0;
+  float *dw;
+} mrec_cin_args;
+
+int32_t mrec_cin_supported(int32_t n_fields, int32_t D, int32_t H_prev, int32_t H,
+                           mrec_dtype x0_dtype, mrec_dtype x_dtype);
+int32_t mrec_cin_field_pitch(int32_t n_fields); /* MP */
+int32_t mrec_cin_fwd_rows(int32_t H);           /* rows of w_fwd */
+int32_t mrec_cin_bwd_cols(int32_t H);           /* columns of w_bwd */
+mrec_status mrec_cin_fwd(const mrec_cin_args *args, mrec_stream stream);
+mrec_status mrec_cin_bwd(const mrec_cin_args *args, mrec_stream stream);
 
 #ifdef __cplusplus
 }

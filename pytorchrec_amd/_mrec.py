@@ -20,7 +20,7 @@ import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("MREC_LIB_PATH") or os.path.join(LIB_DIR, "libmrec.so")
 
-ABI_VERSION = 38
+ABI_VERSION = 39
 MAX_TABLES = 64
 BWD_MAX_BATCH = 8192
 BWD_HASH_MAX_BATCH = 4096  # batches up to this use the hash plan (fusable into a GEMM launch)
@@ -321,6 +321,24 @@ class DotInteractArgs(ctypes.Structure):
                 ("drows", ctypes.c_void_p), ("ld_drows", ctypes.c_int64)]
 
 
+class CinArgs(ctypes.Structure):
+    """mrec_cin_args (include/mrec.h, ABI 39): one CIN layer, both directions."""
+    _fields_ = [("x0", ctypes.c_void_p), ("x0_dtype", ctypes.c_int), ("ld_x0", ctypes.c_int64),
+                ("xp", ctypes.c_void_p), ("xp_dtype", ctypes.c_int), ("ld_xp", ctypes.c_int64),
+                ("w_fwd", ctypes.c_void_p), ("ld_w_fwd", ctypes.c_int64),
+                ("w_bwd", ctypes.c_void_p), ("ld_w_bwd", ctypes.c_int64),
+                ("batch", ctypes.c_int64), ("n_fields", ctypes.c_int32), ("D", ctypes.c_int32),
+                ("H_prev", ctypes.c_int32), ("H", ctypes.c_int32), ("x_dtype", ctypes.c_int),
+                ("xk", ctypes.c_void_p), ("ld_xk", ctypes.c_int64),
+                ("p", ctypes.c_void_p), ("ld_p", ctypes.c_int64),
+                ("dxk", ctypes.c_void_p), ("ld_dxk", ctypes.c_int64),
+                ("dp", ctypes.c_void_p), ("ld_dp", ctypes.c_int64),
+                ("dp_prev", ctypes.c_void_p), ("ld_dp_prev", ctypes.c_int64),
+                ("dxp", ctypes.c_void_p), ("dxp_dtype", ctypes.c_int), ("ld_dxp", ctypes.c_int64),
+                ("dx0", ctypes.c_void_p), ("ld_dx0", ctypes.c_int64),
+                ("dw", ctypes.c_void_p)]
+
+
 LAYOUT_ROW, LAYOUT_COL = 0, 1
 ACT_NONE, ACT_RELU = 0, 1
 
@@ -536,6 +554,12 @@ SIGNATURES = {
                                                      ctypes.c_int]),
     "mrec_dot_interact_fwd": (ctypes.c_int, [ctypes.POINTER(DotInteractArgs), _vp]),
     "mrec_dot_interact_bwd": (ctypes.c_int, [ctypes.POINTER(DotInteractArgs), _vp]),
+    "mrec_cin_supported": (ctypes.c_int32, [_i32, _i32, _i32, _i32, ctypes.c_int, ctypes.c_int]),
+    "mrec_cin_field_pitch": (ctypes.c_int32, [_i32]),
+    "mrec_cin_fwd_rows": (ctypes.c_int32, [_i32]),
+    "mrec_cin_bwd_cols": (ctypes.c_int32, [_i32]),
+    "mrec_cin_fwd": (ctypes.c_int, [ctypes.POINTER(CinArgs), _vp]),
+    "mrec_cin_bwd": (ctypes.c_int, [ctypes.POINTER(CinArgs), _vp]),
     "mrec_tower_fwd_bwd": (ctypes.c_int, [ctypes.POINTER(TowerArgs), _vp]),
     "mrec_tower_image_elems": (ctypes.c_int64, [_i64, _i64, _i32]),
     "mrec_tower_weight_prep": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),

@@ -15,7 +15,8 @@ torch ops, chunked over the items (``retrieval.topk`` decides).  ``shared_negati
 ``mrec_shneg_loss_fwd`` / ``_bwd``, the list-wise losses over a shared pool of negatives, in
 differentiable torch ops (``loss.SharedNegativeLoss`` decides).  ``dot_interact`` is
 ``mrec_dot_interact_fwd`` / ``_bwd``, DLRM's pairwise dot interaction, in the same way
-(``dense.dot_interact`` decides).
+(``dense.dot_interact`` decides).  ``cin`` is ``mrec_cin_fwd`` / ``_bwd``, xDeepFM's Compressed
+Interaction Network, chunked over the batch (``dense.cin`` decides).
 """
 from __future__ import annotations
 
@@ -509,3 +510,106 @@ def dot_interact(bot, rows, F: int, D: int, x_cols: Optional[int] = None, round_
         if x_cols > x.shape[1]:
             x = torch.nn.functional.pad(x, (0, x_cols - x.shape[1]))
     return x if x_dtype is None else x.to(x_dtype)
+
+
+def _cin_layer(x0c, xpc, W, r):
+    """One CIN layer on a batch chunk: x0c [b, m, D], xpc [b, Hp, D], W [H, Hp, m] ->
+    X^k [b, H, D], through Z [b, Hp * m, D] rounded by ``r``."""
+    b, m, D = x0c.shape
+    Z = r((xpc.unsqueeze(2) * x0c.unsqueeze(1)).reshape(b, -1, D))
+    return torch.matmul(W.reshape(W.shape[0], -1), Z)
+
+
+class _CinFn(torch.autograd.Function):
+    """The CIN in torch ops, forward and backward chunked over the batch so that the outer
+    product Z [chunk, H_prev * m, D] exists for one chunk at a time (the backward re-forms
+    it).  ``rnd`` (None or ``bf16_round``) is applied to x0, W, every X^{k-1} that enters a
+    product, Z and dX^k: the kernels' rounding points.  ``store`` rounds X^k where the
+    kernels store it in bf16."""
+
+    @staticmethod
+    def forward(ctx, x0, m, chunk, rnd, store, *weights):
+        B = x0.shape[0]
+        D = x0.shape[1] // m
+        dt = torch.float64 if x0.dtype == torch.float64 else torch.float32
+        r = rnd if rnd is not None else (lambda t: t)
+        st = store if store is not None else (lambda t: t)
+        Ws = [r(w.detach().to(dt)) for w in weights]
+        xs = [torch.empty(B, w.shape[0], D, dtype=dt, device=x0.device) for w in Ws]
+        x0r = r(x0.detach().to(dt).reshape(B, m, D))
+        p = torch.empty(B, sum(w.shape[0] for w in Ws), dtype=dt, device=x0.device)
+        for s in range(0, B, chunk):
+            xp, off = x0r[s:s + chunk], 0
+            for k, W in enumerate(Ws):
+                xk = _cin_layer(x0r[s:s + chunk], xp, W, r)
+                p[s:s + chunk, off:off + W.shape[0]] = xk.sum(2)  # from the unrounded sums
+                off += W.shape[0]
+                xs[k][s:s + chunk] = st(xk)
+                xp = r(xs[k][s:s + chunk])
+        ctx.save_for_backward(x0r, *xs)
+        ctx.Ws, ctx.m, ctx.chunk, ctx.r = Ws, m, chunk, r
+        ctx.in_dtypes = (x0.dtype, [w.dtype for w in weights])
+        return p
+
+    @staticmethod
+    def backward(ctx, dp):
+        x0r, *xs = ctx.saved_tensors
+        Ws, m, chunk, r = ctx.Ws, ctx.m, ctx.chunk, ctx.r
+        B, _, D = x0r.shape
+        dt = x0r.dtype
+        dp = dp.to(dt)
+        offs = [0]
+        for W in Ws:
+            offs.append(offs[-1] + W.shape[0])
+        dx0 = torch.zeros_like(x0r)
+        dWs = [torch.zeros_like(W) for W in Ws]
+        for s in range(0, B, chunk):
+            x0c = x0r[s:s + chunk]
+            b = x0c.shape[0]
+            dxk = None
+            for k in range(len(Ws) - 1, -1, -1):
+                W = Ws[k]
+                H, Hp = W.shape[0], W.shape[1]
+                g = dp[s:s + chunk, offs[k]:offs[k + 1]].unsqueeze(2).expand(b, H, D)
+                g = r(g if dxk is None else dxk + g)
+                xp = x0c if k == 0 else r(xs[k - 1][s:s + chunk])
+                Z = r((xp.unsqueeze(2) * x0c.unsqueeze(1)).reshape(b, Hp * m, D))
+                dWs[k] += torch.einsum("bhd,bnd->hn", g, Z).reshape(H, Hp, m)
+                dZ = torch.matmul(W.reshape(H, -1).t(), g).reshape(b, Hp, m, D)
+                dx0[s:s + chunk] += (dZ * xp.unsqueeze(2)).sum(1)
+                dxk = (dZ * x0c.unsqueeze(1)).sum(2)
+            dx0[s:s + chunk] += dxk
+        x_dt, w_dts = ctx.in_dtypes
+        return (dx0.reshape(B, m * D).to(x_dt), None, None, None, None,
+                *[g.to(t) for g, t in zip(dWs, w_dts)])
+
+
+def cin(x0, weights, round_bf16: bool = False, x_dtype=None, chunk: int = 256):
+    """``mrec_cin_fwd`` / ``_bwd`` over all layers in torch ops (include/mrec.h "CIN"):
+    ``x0 [B, m * D]`` read as [B, m, D] (a strided column slice is fine), ``weights[k - 1]`` =
+    W^k ``[H_k, H_{k-1}, m]`` with H_0 = m ->  ``p [B, sum_k H_k]``,
+    p[b, off_k + h] = sum_d X^k[b, h, d],  X^k[b, h, d] = sum_{i, j} W^k[h, i, j] X^{k-1}[b, i, d]
+    X^0[b, j, d]: identity activation, no bias, every map feeds the output and the next layer.
+    Arithmetic in fp32 (fp64 operands stay fp64).  The outer product Z exists for ``chunk``
+    samples at a time, in the forward and in the backward, which re-forms it.  ``round_bf16``
+    rounds where the kernels round (operands, Z, dX^k; X^k too when ``x_dtype`` is bf16): the
+    GPU path of a shape the kernels do not cover, and their comparator."""
+    weights = list(weights)
+    if not weights:
+        raise ValueError("cin needs at least one layer")
+    m = weights[0].shape[2]
+    if x0.dim() != 2 or x0.shape[1] % m:
+        raise ValueError(f"x0 must be [B, m * D] with m = {m} fields, got {tuple(x0.shape)}")
+    hp = m
+    for w in weights:
+        if w.dim() != 3 or w.shape[1] != hp or w.shape[2] != m:
+            raise ValueError(f"CIN weight must be [H, {hp}, {m}], got {tuple(w.shape)}")
+        hp = w.shape[0]
+    rnd = bf16_round_any if round_bf16 else None
+    store = bf16_round_any if (round_bf16 and x_dtype == torch.bfloat16) else None
+    return _CinFn.apply(x0, m, int(chunk), rnd, store, *weights)
+
+
+def bf16_round_any(t: torch.Tensor) -> torch.Tensor:
+    """nearest bf16 of a detached fp32 / fp64 tensor, in its own dtype."""
+    return t.to(torch.float32).to(torch.bfloat16).to(t.dtype)

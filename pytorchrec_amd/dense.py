@@ -1,5 +1,6 @@
 """Dense-tower ops: Linear(+bias)(+ReLU), DCN-v2 cross, DIN attention pooling, the
-SASRec / GRU4Rec encoders, the NCF scorer, DLRM's pairwise dot interaction.
+SASRec / GRU4Rec encoders, the NCF scorer, DLRM's pairwise dot interaction, xDeepFM's
+Compressed Interaction Network.
 
 One seam for the model code.  On a GPU they run on libmrec's MFMA bf16 GEMM
 (``mrec_gemm``: fp32 accumulation, bias / ReLU / DCN epilogues fused, the fp32
@@ -306,12 +307,13 @@ def weight_prep(W: torch.Tensor, row: bool = True, tr: bool = True):
 
 # bf16 images of an fp32 master weight, cached on the Parameter per kind:
 #   "rowtr": row-major W and W^T (operands of mrec_gemm);
-#   "tower": the MFMA-fragment images of the fused tower (mrec_tower_fwd_bwd).
+#   "tower": the MFMA-fragment images of the fused tower (mrec_tower_fwd_bwd);
+#   "cin":   the forward and transposed images of a CIN layer (mrec_cin_fwd / _bwd).
 # An entry is valid while (weight._version, weight._mrec_gen) is unchanged: torch
 # modifying the weight bumps the version; a kernel updating it in place (fused
 # SGD) re-emits the images it was handed and ``images_updated`` bumps the
 # generation and re-stamps that kind, so only the other kind goes stale.
-_IMG_ATTR = {"rowtr": "_mrec_img", "tower": "_mrec_timg"}
+_IMG_ATTR = {"rowtr": "_mrec_img", "tower": "_mrec_timg", "cin": "_mrec_cimg"}
 
 
 def _img_state(weight):
@@ -1364,6 +1366,145 @@ def dot_interact(bot: Optional[torch.Tensor], rows: torch.Tensor, n_fields: int,
         return _DotInteractFn.apply(bot, rows, F_, D, int(x_cols), x_dtype)
     return cpu_path.dot_interact(bot, rows, F_, D, int(x_cols), round_bf16=rows.is_cuda,
                                  x_dtype=x_dtype)
+
+
+# the fused CIN (mrec_cin_fwd / _bwd, cin.hip) is the default for the compiled shapes; False
+# selects the torch-ops path (the parity tests and the benchmark set it)
+CIN_FUSED = True
+
+
+def cin_supported(m: int, D: int, widths: Sequence[int], x_dtype=torch.float32,
+                  x0_dtype=None) -> bool:
+    """True when the fused CIN covers m fields of D elements, the layer widths (at most 4
+    layers) and the activation dtype.  Decided from the shape alone; never an error."""
+    widths = [int(w) for w in widths]
+    x0_dtype = x0_dtype or x_dtype
+    if not 1 <= len(widths) <= 4 or x_dtype not in _DI_DTYPES or x0_dtype not in _DI_DTYPES:
+        return False
+    lib, hp = _mrec.lib(), int(m)
+    for h in widths:
+        if not lib.mrec_cin_supported(int(m), int(D), hp, h, _mrec.dtype_code(x0_dtype),
+                                      _mrec.dtype_code(x_dtype)):
+            return False
+        hp = h
+    return True
+
+
+def cin_images(weight: torch.Tensor):
+    """(forward, transposed) bf16 images of a CIN weight [H, H_prev, m] (include/mrec.h
+    "CIN": the field pitch and the tile pads are zeros), cached like ``weight_images``."""
+    c = cached_images(weight, "cin")
+    if c is not None:
+        return c
+    W = weight.detach().float()
+    H, Hp, m = W.shape
+    lib = _mrec.lib()
+    MP = int(lib.mrec_cin_field_pitch(m))
+    wf = torch.zeros(int(lib.mrec_cin_fwd_rows(H)), Hp, MP, dtype=_BF16, device=W.device)
+    wf[:H, :, :m] = W
+    wb = torch.zeros((Hp * MP + 31) // 32 * 32, int(lib.mrec_cin_bwd_cols(H)), dtype=_BF16,
+                     device=W.device)
+    wb[:Hp * MP].view(Hp, MP, -1)[:, :m, :H] = W.permute(1, 2, 0)
+    wf = wf.view(wf.shape[0], Hp * MP)
+    weight._mrec_cimg = _img_state(weight) + (wf, wb)
+    return wf, wb
+
+
+class _CinFn(torch.autograd.Function):
+    """p = the CIN's pooled maps of x0: one forward launch per layer, which writes X^k (kept
+    for the backward) and its slice of p; one backward call per layer, top down, each a data
+    gradient launch (dX^{k-1} and the fp32 dX^0 accumulator) and a weight gradient launch."""
+
+    @staticmethod
+    def forward(ctx, x0, m: int, D: int, x_dtype, *weights):
+        B, dev = x0.shape[0], x0.device
+        x0r = _rows16(x0.detach())
+        widths = [w.shape[0] for w in weights]
+        p = torch.empty(B, sum(widths), dtype=torch.float32, device=dev)
+        st = _mrec.stream_handle()
+        args, xs, keep = [], [], []
+        xp, hp, off = x0r, m, 0
+        for w in weights:
+            H = w.shape[0]
+            wf, wb = cin_images(w)
+            xk = _alloc(B, H * D, x_dtype, dev)
+            a = _mrec.CinArgs()
+            a.x0, a.x0_dtype, a.ld_x0 = x0r.data_ptr(), _mrec.dtype_code(x0r.dtype), x0r.stride(0)
+            a.xp, a.xp_dtype, a.ld_xp = xp.data_ptr(), _mrec.dtype_code(xp.dtype), xp.stride(0)
+            a.w_fwd, a.ld_w_fwd, a.w_bwd, a.ld_w_bwd = wf.data_ptr(), wf.stride(0), wb.data_ptr(), wb.stride(0)
+            a.batch, a.n_fields, a.D, a.H_prev, a.H = B, int(m), int(D), int(hp), int(H)
+            a.x_dtype = _mrec.dtype_code(x_dtype)
+            a.xk, a.ld_xk = xk.data_ptr(), xk.stride(0)
+            a.p, a.ld_p = p.data_ptr() + 4 * off, p.stride(0)
+            if B:
+                _mrec.call("mrec_cin_fwd", ctypes.byref(a), st)
+            args.append(a)
+            xs.append(xk)
+            keep.append((wf, wb))
+            xp, hp, off = xk, H, off + H
+        ctx.args, ctx.keep, ctx.weights = args, (x0r, xs, keep), weights
+        ctx.x0_dtype = x0.dtype
+        return p
+
+    @staticmethod
+    def backward(ctx, dp):
+        args, (x0r, xs, keep), weights = ctx.args, ctx.keep, ctx.weights
+        B, dev = x0r.shape[0], x0r.device
+        m, D = int(args[0].n_fields), int(args[0].D)
+        dp = dp.detach().float().contiguous()
+        dx0 = torch.zeros(B, m * D, dtype=torch.float32, device=dev)
+        st = _mrec.stream_handle()
+        offs = [0]
+        for w in weights:
+            offs.append(offs[-1] + w.shape[0])
+        dws, dxk = [None] * len(weights), None
+        for k in range(len(weights) - 1, -1, -1):
+            a = args[k]
+            H, Hp = int(a.H), int(a.H_prev)
+            if dxk is not None:
+                a.dxk, a.ld_dxk = dxk.data_ptr(), dxk.stride(0)
+            a.dp, a.ld_dp = dp.data_ptr() + 4 * offs[k], dp.stride(0)
+            if k > 0:
+                a.dp_prev, a.ld_dp_prev = dp.data_ptr() + 4 * offs[k - 1], dp.stride(0)
+            dxp = _alloc(B, Hp * D, xs[k - 1].dtype if k > 0 else torch.float32, dev)
+            a.dxp, a.dxp_dtype, a.ld_dxp = dxp.data_ptr(), _mrec.dtype_code(dxp.dtype), dxp.stride(0)
+            a.dx0, a.ld_dx0 = dx0.data_ptr(), dx0.stride(0)
+            dw = torch.empty(H, Hp, m, dtype=torch.float32, device=dev)
+            a.dw = dw.data_ptr()
+            if B:
+                _mrec.call("mrec_cin_bwd", ctypes.byref(a), st)
+            else:
+                dw.zero_()
+            dws[k], dxk = dw, dxp
+        if B:
+            dx0 += dxk  # layer 1: X^0 is also the X^{k-1} operand
+        ctx.args = ctx.keep = ctx.weights = None
+        return (dx0.to(ctx.x0_dtype), None, None, None,
+                *[g.to(w.dtype) for g, w in zip(dws, weights)])
+
+
+def cin(x0: torch.Tensor, n_fields: int, weights, x_dtype=None) -> torch.Tensor:
+    """xDeepFM's Compressed Interaction Network (include/mrec.h "CIN"): ``x0 [B, n_fields * D]``
+    read as [B, m, D] (a column slice of the interact launch's x0 rows is fine),
+    ``weights[k - 1]`` = W^k [H_k, H_{k-1}, m] with H_0 = m ->  p ``[B, sum_k H_k]`` fp32, the
+    maps X^k summed over d.  X^k is kept in ``x_dtype`` (default: x0's).  On a GPU the fused
+    kernels for the compiled shapes; else, and on the CPU, the same contract as torch ops
+    chunked over the batch (``cpu_path.cin``), rounding on a GPU where the kernels round."""
+    from pytorchrec_amd import cpu_path
+    weights = list(weights)
+    m = int(n_fields)
+    if m < 1 or x0.dim() != 2 or x0.shape[1] % m:
+        raise ValueError(f"x0 must be [B, n_fields * D], got {tuple(x0.shape)} for {m} fields")
+    if not weights or weights[0].shape[2] != m:
+        raise ValueError(f"CIN weights must be [H_k, H_(k-1), {m}], one per layer")
+    D = x0.shape[1] // m
+    x_dtype = x_dtype or x0.dtype
+    if (x0.is_cuda and CIN_FUSED and all(w.dim() == 3 for w in weights)
+            and cin_supported(m, D, [w.shape[0] for w in weights], x_dtype, x0.dtype)
+            and all(w.shape[1] == h and w.shape[2] == m
+                    for w, h in zip(weights, [m] + [w.shape[0] for w in weights[:-1]]))):
+        return _CinFn.apply(x0, m, D, x_dtype, *weights)
+    return cpu_path.cin(x0, weights, round_bf16=x0.is_cuda, x_dtype=x_dtype)
 
 
 def colsum(s: torch.Tensor, X: Optional[torch.Tensor], want_total: bool = True, *,

@@ -11,6 +11,7 @@ from pytorchrec_amd.model.IModel import IModel
 from pytorchrec_amd.model.NCF import NCF
 from pytorchrec_amd.model.SASRec import SASRec
 from pytorchrec_amd.model.SVDPP import SVDPP
+from pytorchrec_amd.model.XDeepFM import XDeepFM
 
 _model_classes: Dict[str, Type[IModel]] = {
     "funksvd": FunkSVD,
@@ -23,6 +24,7 @@ _model_classes: Dict[str, Type[IModel]] = {
     "dcnv2": DCNv2,
     "din": DIN,
     "dlrm": DLRM,
+    "xdeepfm": XDeepFM,
 }
 
 model_name_list = _model_classes.keys()
