@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MREC_ABI_VERSION 39
+#define MREC_ABI_VERSION 40
 #define MREC_MAX_TABLES 64      /* tables per table bank / per call */
 #define MREC_BWD_MAX_BATCH 8192  /* lookups per table per plan/apply call */
 #define MREC_BWD_HASH_MAX_BATCH 4096  /* batches up to this use the hash plan */
@@ -2053,6 +2053,86 @@ int32_t mrec_cin_fwd_rows(int32_t H);           /* rows of w_fwd */
 int32_t mrec_cin_bwd_cols(int32_t H);           /* columns of w_bwd */
 mrec_status mrec_cin_fwd(const mrec_cin_args *args, mrec_stream stream);
 mrec_status mrec_cin_bwd(const mrec_cin_args *args, mrec_stream stream);
+
+/* ------------------------------------------------------------------------- */
+/* AutoInt: one interacting layer (multi-head self-attention over the fields)  */
+/* per call (ABI 40; csrc/autoint.hip)                                         */
+/* ------------------------------------------------------------------------- */
+/*
+ * With m = n_fields, X = x read as [batch, m, d_in] (row stride ld_x), A = heads * head_dim
+ * and the weights Wq, Wk, Wv, Wres in nn.Linear layout [A, d_in] (Wres optional: has_res):
+ *   Q = X Wq^T, K = X Wk^T, V = X Wv^T                 [m, A], heads of head_dim columns
+ *   S_h = scale * Q_h K_h^T                            [m, m] per head
+ *   P_h = softmax over the keys (last index), shifted by the row's own maximum
+ *   O   = [P_1 V_1 | .. | P_heads V_heads]             [m, A]
+ *   Y   = relu(O + X Wres^T)                           y [batch, m * A], row stride ld_y
+ * No mask, no bias, no dropout, no LayerNorm.
+ *   Rounding.  X, the weights (through their bf16 images) and dY enter the products as bf16
+ * (RNE where stored in fp32).  Accumulation is fp32 (MFMA).  Q, K, V are rounded once to
+ * bf16.  S and the softmax are fp32 (exp, a true division by the sum).  P is rounded once to
+ * bf16 before P V.  O + X Wres^T is added in fp32.  Y is rounded once when y_dtype is
+ * MREC_BF16.  In the backward scale * dS, dQ, dK and dV are each rounded once to bf16 before
+ * the product that consumes them; the softmax derivative uses the fp32 P.
+ *   Weight images (bf16, built by the caller whenever a weight changes):
+ *   w_fwd [mrec_autoint_image_rows(A) = 4 A][d_in]   rows [Wres | Wq | Wk | Wv]
+ *   w_bwd [d_in][4 A]                                 its transpose
+ * Without Wres its rows are zeros and has_res is 0.
+ *   Backward (mrec_autoint_bwd: a data-gradient launch, a weight-gradient launch and the sum
+ * of its partials).  y is the forward's output, an input here; dZ = dY * (Y > 0):
+ *   dV_h = P_h^T dZ_h      dP_h = dZ_h V_h^T      dS_h = P_h * (dP_h - rowsum(dP_h * P_h))
+ *   dQ_h = scale * dS_h K_h       dK_h = scale * dS_h^T Q_h
+ *   dx   = dQ Wq + dK Wk + dV Wv + dZ Wres          rounded once into dx_dtype, overwritten
+ *   dw   = sum over batch and fields of (dQ | dK | dV | dZ)^T X
+ * dw is contiguous fp32 [4 (3 without Wres)][A][d_in] in the order q, k, v, res, overwritten.
+ * Q, K, V, S and P are recomputed from x: nothing but x and y is kept between the directions.
+ * workspace (16-byte aligned, mrec_autoint_bwd_workspace_size bytes) holds the transposed
+ * (dZ | dQ | dK | dV) rows in bf16 and the weight gradient's per-workgroup fp32 partials.
+ *   Determinism: no atomics; y and dx of a sample depend on that sample alone; dw is summed
+ * over each workgroup's own samples in order, then over the workgroups in order.
+ *   One description for both directions: the forward ignores dy, dx, dw, w_bwd and the
+ * workspace.
+ * Compiled shapes (mrec_autoint_supported): 2 <= n_fields <= 32, d_in in {8, 16, 32, 64}, A
+ * in {16, 32, 64}, head_dim in {8, 16, 32} dividing A; x, y, dy, dx each MREC_F32 or
+ * MREC_BF16 with 16-byte aligned rows.  batch = 0 launches nothing.  Never read or written:
+ * columns past the stated widths, rows >= batch.  Anything else is MREC_EINVAL with
+ * mrec_last_error() before any launch.
+ */
+typedef struct {
+  const void *x;
+  mrec_dtype x_dtype;
+  int64_t ld_x;
+  const void *w_fwd;
+  int64_t ld_w_fwd;
+  const void *w_bwd;
+  int64_t ld_w_bwd;
+  int32_t has_res;
+  int64_t batch;
+  int32_t n_fields;
+  int32_t d_in;
+  int32_t heads;
+  int32_t head_dim;
+  int32_t A;
+  float scale;
+  void *y; /* written by the forward, read by the backward */
+  mrec_dtype y_dtype;
+  int64_t ld_y;
+  const void *dy;
+  mrec_dtype dy_dtype;
+  int64_t ld_dy;
+  void *dx;
+  mrec_dtype dx_dtype;
+  int64_t ld_dx;
+  float *dw;
+  void *workspace;
+  int64_t workspace_bytes;
+} mrec_autoint_args;
+
+int32_t mrec_autoint_supported(int32_t n_fields, int32_t d_in, int32_t heads, int32_t head_dim,
+                               mrec_dtype x_dtype, mrec_dtype y_dtype);
+int32_t mrec_autoint_image_rows(int32_t A); /* rows of w_fwd = columns of w_bwd */
+int64_t mrec_autoint_bwd_workspace_size(int64_t batch, int32_t d_in, int32_t A);
+mrec_status mrec_autoint_fwd(const mrec_autoint_args *args, mrec_stream stream);
+mrec_status mrec_autoint_bwd(const mrec_autoint_args *args, mrec_stream stream);
 
 #ifdef __cplusplus
 }

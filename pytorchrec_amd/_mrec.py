@@ -20,7 +20,7 @@ import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("MREC_LIB_PATH") or os.path.join(LIB_DIR, "libmrec.so")
 
-ABI_VERSION = 39
+ABI_VERSION = 40
 MAX_TABLES = 64
 BWD_MAX_BATCH = 8192
 BWD_HASH_MAX_BATCH = 4096  # batches up to this use the hash plan (fusable into a GEMM launch)
@@ -339,6 +339,23 @@ class CinArgs(ctypes.Structure):
                 ("dw", ctypes.c_void_p)]
 
 
+class AutoIntArgs(ctypes.Structure):
+    """mrec_autoint_args (include/mrec.h, ABI 40): one AutoInt interacting layer, both
+    directions."""
+    _fields_ = [("x", ctypes.c_void_p), ("x_dtype", ctypes.c_int), ("ld_x", ctypes.c_int64),
+                ("w_fwd", ctypes.c_void_p), ("ld_w_fwd", ctypes.c_int64),
+                ("w_bwd", ctypes.c_void_p), ("ld_w_bwd", ctypes.c_int64),
+                ("has_res", ctypes.c_int32), ("batch", ctypes.c_int64),
+                ("n_fields", ctypes.c_int32), ("d_in", ctypes.c_int32),
+                ("heads", ctypes.c_int32), ("head_dim", ctypes.c_int32), ("A", ctypes.c_int32),
+                ("scale", ctypes.c_float),
+                ("y", ctypes.c_void_p), ("y_dtype", ctypes.c_int), ("ld_y", ctypes.c_int64),
+                ("dy", ctypes.c_void_p), ("dy_dtype", ctypes.c_int), ("ld_dy", ctypes.c_int64),
+                ("dx", ctypes.c_void_p), ("dx_dtype", ctypes.c_int), ("ld_dx", ctypes.c_int64),
+                ("dw", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+                ("workspace_bytes", ctypes.c_int64)]
+
+
 LAYOUT_ROW, LAYOUT_COL = 0, 1
 ACT_NONE, ACT_RELU = 0, 1
 
@@ -560,6 +577,11 @@ SIGNATURES = {
     "mrec_cin_bwd_cols": (ctypes.c_int32, [_i32]),
     "mrec_cin_fwd": (ctypes.c_int, [ctypes.POINTER(CinArgs), _vp]),
     "mrec_cin_bwd": (ctypes.c_int, [ctypes.POINTER(CinArgs), _vp]),
+    "mrec_autoint_supported": (ctypes.c_int32, [_i32, _i32, _i32, _i32, ctypes.c_int, ctypes.c_int]),
+    "mrec_autoint_image_rows": (ctypes.c_int32, [_i32]),
+    "mrec_autoint_bwd_workspace_size": (ctypes.c_int64, [_i64, _i32, _i32]),
+    "mrec_autoint_fwd": (ctypes.c_int, [ctypes.POINTER(AutoIntArgs), _vp]),
+    "mrec_autoint_bwd": (ctypes.c_int, [ctypes.POINTER(AutoIntArgs), _vp]),
     "mrec_tower_fwd_bwd": (ctypes.c_int, [ctypes.POINTER(TowerArgs), _vp]),
     "mrec_tower_image_elems": (ctypes.c_int64, [_i64, _i64, _i32]),
     "mrec_tower_weight_prep": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),

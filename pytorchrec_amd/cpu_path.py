@@ -16,7 +16,9 @@ torch ops, chunked over the items (``retrieval.topk`` decides).  ``shared_negati
 differentiable torch ops (``loss.SharedNegativeLoss`` decides).  ``dot_interact`` is
 ``mrec_dot_interact_fwd`` / ``_bwd``, DLRM's pairwise dot interaction, in the same way
 (``dense.dot_interact`` decides).  ``cin`` is ``mrec_cin_fwd`` / ``_bwd``, xDeepFM's Compressed
-Interaction Network, chunked over the batch (``dense.cin`` decides).
+Interaction Network, chunked over the batch (``dense.cin`` decides).  ``autoint`` is
+``mrec_autoint_fwd`` / ``_bwd``, AutoInt's interacting layers, in the same way
+(``dense.autoint`` decides).
 """
 from __future__ import annotations
 
@@ -613,3 +615,118 @@ def cin(x0, weights, round_bf16: bool = False, x_dtype=None, chunk: int = 256):
 def bf16_round_any(t: torch.Tensor) -> torch.Tensor:
     """nearest bf16 of a detached fp32 / fp64 tensor, in its own dtype."""
     return t.to(torch.float32).to(torch.bfloat16).to(t.dtype)
+
+
+def _ste(rnd):
+    """``rnd`` as a straight-through rounding: the value is rounded, the gradient passes."""
+    if rnd is None:
+        return lambda t: t
+    return lambda t: t + (rnd(t.detach()) - t.detach())
+
+
+def _autoint_layer(X, Wq, Wk, Wv, Wres, heads, scale, r, st):
+    """One interacting layer on a batch chunk: X [b, m, d_in] and the weights [A, d_in], both
+    already rounded -> Y [b, m, A].  ``r`` rounds Q, K, V and P, ``st`` rounds Y."""
+    b, m, _ = X.shape
+    A = Wq.shape[0]
+    hd = A // heads
+    q = r(X @ Wq.t()).view(b, m, heads, hd).transpose(1, 2)
+    k = r(X @ Wk.t()).view(b, m, heads, hd).transpose(1, 2)
+    v = r(X @ Wv.t()).view(b, m, heads, hd).transpose(1, 2)
+    P = torch.softmax(scale * (q @ k.transpose(-1, -2)), dim=-1)  # shifted by the row's maximum
+    O = (r(P) @ v).transpose(1, 2).reshape(b, m, A)
+    if Wres is not None:
+        O = O + X @ Wres.t()
+    return st(torch.relu(O))
+
+
+def _autoint_stack(xc, m, flat, has_res, heads, scale, rnd, store):
+    """All layers on a chunk: xc [b, m * d_in] -> [b, m * A_last], in xc's arithmetic dtype."""
+    r, st = _ste(rnd), _ste(store)
+    X = r(xc.reshape(xc.shape[0], m, -1))
+    it = iter(flat)
+    for k, res in enumerate(has_res):
+        Wq, Wk, Wv = r(next(it)), r(next(it)), r(next(it))
+        Wres = r(next(it)) if res else None
+        Y = _autoint_layer(X, Wq, Wk, Wv, Wres, heads, scale, r, st)
+        X = r(Y) if k + 1 < len(has_res) else Y
+    return X.reshape(X.shape[0], -1)
+
+
+class _AutoIntFn(torch.autograd.Function):
+    """The interacting stack in torch ops, forward and backward chunked over the batch: the
+    [chunk, heads, m, m] scores exist for one chunk at a time, and the backward recomputes
+    them from x0 (nothing else is kept), as the kernels do."""
+
+    @staticmethod
+    def forward(ctx, x0, meta, *flat):
+        m, has_res, heads, scale, chunk, rnd, store = meta
+        dt = torch.float64 if x0.dtype == torch.float64 else torch.float32
+        ws = [w.detach().to(dt) for w in flat]
+        xs = x0.detach().to(dt).contiguous()
+        with torch.no_grad():
+            ys = [_autoint_stack(xs[s:s + chunk], m, ws, has_res, heads, scale, rnd, store)
+                  for s in range(0, x0.shape[0], chunk)]
+        A = flat[-(4 if has_res[-1] else 3)].shape[0]  # the last layer's Wq
+        y = torch.cat(ys) if ys else xs.new_zeros(0, m * A)
+        ctx.save_for_backward(x0, *flat)
+        ctx.meta = meta
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x0, *flat = ctx.saved_tensors
+        m, has_res, heads, scale, chunk, rnd, store = ctx.meta
+        dt = torch.float64 if x0.dtype == torch.float64 else torch.float32
+        ws = [w.detach().to(dt).requires_grad_(True) for w in flat]
+        dx = torch.zeros(x0.shape, dtype=dt, device=x0.device)
+        dws = [torch.zeros_like(w) for w in ws]
+        dy = _ste(rnd)(dy.detach().to(dt))
+        for s in range(0, x0.shape[0], chunk):
+            with torch.enable_grad():
+                xc = x0[s:s + chunk].detach().to(dt).contiguous().requires_grad_(True)
+                y = _autoint_stack(xc, m, ws, has_res, heads, scale, rnd, store)
+                gs = torch.autograd.grad(y, [xc] + ws, dy[s:s + chunk])
+            dx[s:s + chunk] = gs[0]
+            for a, g in zip(dws, gs[1:]):
+                a += g
+        return (dx.to(x0.dtype), None, *[g.to(w.dtype) for g, w in zip(dws, flat)])
+
+
+def autoint(x0, layers, heads: int, scale: float = 1.0, round_bf16: bool = False, x_dtype=None,
+            chunk: int = 256):
+    """``mrec_autoint_fwd`` / ``_bwd`` over all layers in torch ops (include/mrec.h
+    "AutoInt"): ``x0 [B, m * d_in]`` read as [B, m, d_in] (a strided column slice is fine),
+    ``layers[k]`` = ``(Wq, Wk, Wv, Wres or None)`` in nn.Linear layout ``[A_k, A_(k-1)]`` ->
+    ``[B, m * A_last]``.  Per layer Q, K, V = X W^T split into ``heads`` heads, P = softmax over
+    the keys of scale * Q_h K_h^T, Y = relu([P_h V_h] + X Wres^T).  Arithmetic in fp32 (fp64
+    operands stay fp64).  The scores exist for ``chunk`` samples at a time in both directions;
+    the backward recomputes them.  ``round_bf16`` rounds exactly where the kernels' forward
+    rounds: the operands (X, the weights, dY), Q K V, P, and Y when ``x_dtype`` is bf16; S, the
+    softmax and O + X Wres^T stay unrounded.  The result comes in ``x_dtype`` (default: x0's).
+    The GPU path of a shape the kernels do not cover, and their comparator."""
+    layers = [tuple(l) for l in layers]
+    if not layers:
+        raise ValueError("autoint needs at least one layer")
+    d_in = layers[0][0].shape[1]
+    if x0.dim() != 2 or x0.shape[1] % d_in:
+        raise ValueError(f"x0 must be [B, m * {d_in}], got {tuple(x0.shape)}")
+    m, heads = x0.shape[1] // d_in, int(heads)
+    flat, has_res, d = [], [], d_in
+    for l in layers:
+        if len(l) != 4:
+            raise ValueError("a layer is (Wq, Wk, Wv, Wres or None)")
+        A = l[0].shape[0]
+        if heads < 1 or A % heads:
+            raise ValueError(f"heads = {heads} does not divide the layer width {A}")
+        for w in l:
+            if w is not None and tuple(w.shape) != (A, d):
+                raise ValueError(f"AutoInt weight must be [{A}, {d}], got {tuple(w.shape)}")
+        flat += [w for w in l if w is not None]
+        has_res.append(l[3] is not None)
+        d = A
+    rnd = bf16_round_any if round_bf16 else None
+    store = bf16_round_any if (round_bf16 and x_dtype == torch.bfloat16) else None
+    meta = (m, tuple(has_res), heads, float(scale), int(chunk), rnd, store)
+    y = _AutoIntFn.apply(x0, meta, *flat)
+    return y.to(x_dtype or x0.dtype)

@@ -1,6 +1,6 @@
 """Dense-tower ops: Linear(+bias)(+ReLU), DCN-v2 cross, DIN attention pooling, the
 SASRec / GRU4Rec encoders, the NCF scorer, DLRM's pairwise dot interaction, xDeepFM's
-Compressed Interaction Network.
+Compressed Interaction Network, AutoInt's interacting (field self-attention) layers.
 
 One seam for the model code.  On a GPU they run on libmrec's MFMA bf16 GEMM
 (``mrec_gemm``: fp32 accumulation, bias / ReLU / DCN epilogues fused, the fp32
@@ -308,12 +308,15 @@ def weight_prep(W: torch.Tensor, row: bool = True, tr: bool = True):
 # bf16 images of an fp32 master weight, cached on the Parameter per kind:
 #   "rowtr": row-major W and W^T (operands of mrec_gemm);
 #   "tower": the MFMA-fragment images of the fused tower (mrec_tower_fwd_bwd);
-#   "cin":   the forward and transposed images of a CIN layer (mrec_cin_fwd / _bwd).
+#   "cin":   the forward and transposed images of a CIN layer (mrec_cin_fwd / _bwd);
+#   "autoint": the [Wres | Wq | Wk | Wv] image of an AutoInt layer and its transpose, kept on
+#            Wq (mrec_autoint_fwd / _bwd).
 # An entry is valid while (weight._version, weight._mrec_gen) is unchanged: torch
 # modifying the weight bumps the version; a kernel updating it in place (fused
 # SGD) re-emits the images it was handed and ``images_updated`` bumps the
 # generation and re-stamps that kind, so only the other kind goes stale.
-_IMG_ATTR = {"rowtr": "_mrec_img", "tower": "_mrec_timg", "cin": "_mrec_cimg"}
+_IMG_ATTR = {"rowtr": "_mrec_img", "tower": "_mrec_timg", "cin": "_mrec_cimg",
+             "autoint": "_mrec_aimg"}
 
 
 def _img_state(weight):
@@ -1505,6 +1508,160 @@ def cin(x0: torch.Tensor, n_fields: int, weights, x_dtype=None) -> torch.Tensor:
                     for w, h in zip(weights, [m] + [w.shape[0] for w in weights[:-1]]))):
         return _CinFn.apply(x0, m, D, x_dtype, *weights)
     return cpu_path.cin(x0, weights, round_bf16=x0.is_cuda, x_dtype=x_dtype)
+
+
+# the fused AutoInt interacting layers (mrec_autoint_fwd / _bwd, autoint.hip) are the default
+# for the compiled shapes; False selects the torch-ops path (the parity tests and the
+# benchmark set it)
+AUTOINT_FUSED = True
+
+
+def _autoint_dims(m: int, d_in: int, layers, heads: int):
+    """[(d_in_k, A_k, head_dim_k)] of well-formed layers, else None."""
+    dims, d = [], int(d_in)
+    for l in layers:
+        if len(l) != 4 or any(w is not None and (w.dim() != 2 or tuple(w.shape) != (l[0].shape[0], d))
+                              for w in l) or any(w is None for w in l[:3]):
+            return None
+        A = l[0].shape[0]
+        if heads < 1 or A % heads:
+            return None
+        dims.append((d, A, A // heads))
+        d = A
+    return dims
+
+
+def autoint_supported(m: int, d_in: int, widths: Sequence[int], heads: int,
+                      x_dtype=torch.float32, x0_dtype=None) -> bool:
+    """True when the fused interacting layers cover m fields of d_in elements, the layer widths
+    A_k = heads * head_dim_k (at most 4 layers) and the activation dtypes.  Decided from the
+    shape alone; never an error."""
+    widths = [int(w) for w in widths]
+    x0_dtype = x0_dtype or x_dtype
+    heads = int(heads)
+    if (not 1 <= len(widths) <= 4 or heads < 1 or x_dtype not in _DI_DTYPES
+            or x0_dtype not in _DI_DTYPES or any(w < 1 or w % heads for w in widths)):
+        return False
+    lib, d, xd = _mrec.lib(), int(d_in), x0_dtype
+    for A in widths:
+        if not lib.mrec_autoint_supported(int(m), d, heads, A // heads, _mrec.dtype_code(xd),
+                                          _mrec.dtype_code(x_dtype)):
+            return False
+        d, xd = A, x_dtype
+    return True
+
+
+def autoint_images(Wq, Wk, Wv, Wres):
+    """(forward, transposed) bf16 images of one interacting layer (include/mrec.h "AutoInt":
+    rows [Wres | Wq | Wk | Wv], zeros without Wres), cached on Wq like ``weight_images`` and
+    valid while none of the four weights changed."""
+    others = tuple((id(w), _img_state(w)) for w in (Wk, Wv, Wres) if w is not None)
+    c = cached_images(Wq, "autoint")
+    if c is not None and Wq._mrec_aimg[4] == others:
+        return c
+    A, d = Wq.shape
+    rows = int(_mrec.lib().mrec_autoint_image_rows(A))
+    wf = torch.zeros(rows, d, dtype=_BF16, device=Wq.device)
+    for k, w in ((1, Wq), (2, Wk), (3, Wv), (0, Wres)):
+        if w is not None:
+            wf[k * A:(k + 1) * A] = w.detach()
+    wb = wf.t().contiguous()
+    Wq._mrec_aimg = _img_state(Wq) + (wf, wb, others)
+    return wf, wb
+
+
+class _AutoIntFn(torch.autograd.Function):
+    """The interacting stack: one forward launch per layer bottom up, each writing the
+    layer's Y (kept: it is the next layer's input and the backward's ReLU mask); one backward
+    call per layer top down (dx, then dw through the caller's workspace)."""
+
+    @staticmethod
+    def forward(ctx, x0, m: int, heads: int, scale: float, x_dtype, has_res, *flat):
+        B, dev = x0.shape[0], x0.device
+        xs = [_rows16(x0.detach())]
+        st = _mrec.stream_handle()
+        args, keep, it = [], [], iter(flat)
+        for res in has_res:
+            Wq, Wk, Wv = next(it), next(it), next(it)
+            Wres = next(it) if res else None
+            A, d = Wq.shape
+            wf, wb = autoint_images(Wq, Wk, Wv, Wres)
+            x = xs[-1]
+            y = _alloc(B, m * A, x_dtype, dev)
+            a = _mrec.AutoIntArgs()
+            a.x, a.x_dtype, a.ld_x = x.data_ptr(), _mrec.dtype_code(x.dtype), x.stride(0)
+            a.w_fwd, a.ld_w_fwd, a.w_bwd, a.ld_w_bwd = wf.data_ptr(), wf.stride(0), wb.data_ptr(), wb.stride(0)
+            a.has_res, a.batch, a.n_fields, a.d_in = int(res), B, int(m), int(d)
+            a.heads, a.head_dim, a.A, a.scale = int(heads), int(A // heads), int(A), float(scale)
+            a.y, a.y_dtype, a.ld_y = y.data_ptr(), _mrec.dtype_code(y.dtype), y.stride(0)
+            if B:
+                _mrec.call("mrec_autoint_fwd", ctypes.byref(a), st)
+            args.append(a)
+            keep.append((wf, wb))
+            xs.append(y)
+        ctx.args, ctx.keep, ctx.flat, ctx.has_res = args, (xs, keep), flat, has_res
+        ctx.x0_dtype = x0.dtype
+        return xs[-1]
+
+    @staticmethod
+    def backward(ctx, dy):
+        args, (xs, keep), flat, has_res = ctx.args, ctx.keep, ctx.flat, ctx.has_res
+        B, dev = xs[0].shape[0], xs[0].device
+        lib, st = _mrec.lib(), _mrec.stream_handle()
+        dy = dy.detach()
+        if dy.dtype not in _DI_DTYPES:
+            dy = dy.float()
+        dy = _rows16(dy)
+        ws_bytes = max([int(lib.mrec_autoint_bwd_workspace_size(B, int(a.d_in), int(a.A))) for a in args] + [16])
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        dws = [None] * len(args)
+        for k in range(len(args) - 1, -1, -1):
+            a = args[k]
+            dx = _alloc(B, int(a.n_fields) * int(a.d_in), xs[k].dtype, dev)
+            dw = torch.empty(4 if has_res[k] else 3, int(a.A), int(a.d_in), dtype=torch.float32, device=dev)
+            a.dy, a.dy_dtype, a.ld_dy = dy.data_ptr(), _mrec.dtype_code(dy.dtype), dy.stride(0)
+            a.dx, a.dx_dtype, a.ld_dx = dx.data_ptr(), _mrec.dtype_code(dx.dtype), dx.stride(0)
+            a.dw, a.workspace, a.workspace_bytes = dw.data_ptr(), ws.data_ptr(), ws_bytes
+            if B:
+                _mrec.call("mrec_autoint_bwd", ctypes.byref(a), st)
+            else:
+                dw.zero_()
+            dws[k], dy = dw, dx
+        grads = []
+        it = iter(flat)
+        for k, res in enumerate(has_res):
+            for j in range(4 if res else 3):
+                grads.append(dws[k][j].to(next(it).dtype))
+        ctx.args = ctx.keep = ctx.flat = None
+        return (dy.to(ctx.x0_dtype), None, None, None, None, None, *grads)
+
+
+def autoint(x0: torch.Tensor, n_fields: int, layers, heads: int, scale: float = 1.0,
+            x_dtype=None) -> torch.Tensor:
+    """AutoInt's interacting stack (include/mrec.h "AutoInt"): ``x0 [B, n_fields * d_in]`` read
+    as [B, m, d_in] (a column slice of the interact launch's x0 rows is fine), ``layers`` a
+    sequence of ``(Wq, Wk, Wv, Wres or None)`` in nn.Linear layout -> ``[B, m * A_last]``, every
+    layer multi-head self-attention over the fields, a residual projection and a ReLU.  The
+    layers' outputs are kept in ``x_dtype`` (default: x0's).  On a GPU the fused kernels for the
+    compiled shapes; else, and on the CPU, the same contract as torch ops chunked over the batch
+    (``cpu_path.autoint``), rounding on a GPU where the kernels round."""
+    from pytorchrec_amd import cpu_path
+    layers = [tuple(l) for l in layers]
+    m, heads = int(n_fields), int(heads)
+    if m < 1 or x0.dim() != 2 or x0.shape[1] % m:
+        raise ValueError(f"x0 must be [B, n_fields * d_in], got {tuple(x0.shape)} for {m} fields")
+    if not layers:
+        raise ValueError("autoint needs at least one layer (Wq, Wk, Wv, Wres or None)")
+    d_in = x0.shape[1] // m
+    x_dtype = x_dtype or x0.dtype
+    if x0.is_cuda and AUTOINT_FUSED:
+        dims = _autoint_dims(m, d_in, layers, heads)
+        if dims is not None and autoint_supported(m, d_in, [A for _, A, _ in dims], heads, x_dtype,
+                                                  x0.dtype):
+            has_res = tuple(l[3] is not None for l in layers)
+            flat = [w for l in layers for w in l if w is not None]
+            return _AutoIntFn.apply(x0, m, heads, float(scale), x_dtype, has_res, *flat)
+    return cpu_path.autoint(x0, layers, heads, scale, round_bf16=x0.is_cuda, x_dtype=x_dtype)
 
 
 def colsum(s: torch.Tensor, X: Optional[torch.Tensor], want_total: bool = True, *,

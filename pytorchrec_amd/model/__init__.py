@@ -5,6 +5,7 @@ from pytorchrec_amd.model.DCNv2 import DCNv2
 from pytorchrec_amd.model.DIN import DIN
 from pytorchrec_amd.model.DLRM import DLRM
 from pytorchrec_amd.model.XDeepFM import XDeepFM
+from pytorchrec_amd.model.AutoInt import AutoInt
 from pytorchrec_amd.model.FunkSVD import FunkSVD
 from pytorchrec_amd.model.SVDPP import SVDPP
 from pytorchrec_amd.model.SASRec import SASRec

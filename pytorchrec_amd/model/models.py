@@ -12,6 +12,7 @@ from pytorchrec_amd.model.NCF import NCF
 from pytorchrec_amd.model.SASRec import SASRec
 from pytorchrec_amd.model.SVDPP import SVDPP
 from pytorchrec_amd.model.XDeepFM import XDeepFM
+from pytorchrec_amd.model.AutoInt import AutoInt
 
 _model_classes: Dict[str, Type[IModel]] = {
     "funksvd": FunkSVD,
@@ -25,6 +26,7 @@ _model_classes: Dict[str, Type[IModel]] = {
     "din": DIN,
     "dlrm": DLRM,
     "xdeepfm": XDeepFM,
+    "autoint": AutoInt,
 }
 
 model_name_list = _model_classes.keys()
