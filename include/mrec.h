@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MREC_ABI_VERSION 40
+#define MREC_ABI_VERSION 41
 #define MREC_MAX_TABLES 64      /* tables per table bank / per call */
 #define MREC_BWD_MAX_BATCH 8192  /* lookups per table per plan/apply call */
 #define MREC_BWD_HASH_MAX_BATCH 4096  /* batches up to this use the hash plan */
@@ -2133,6 +2133,96 @@ int32_t mrec_autoint_image_rows(int32_t A); /* rows of w_fwd = columns of w_bwd 
 int64_t mrec_autoint_bwd_workspace_size(int64_t batch, int32_t d_in, int32_t A);
 mrec_status mrec_autoint_fwd(const mrec_autoint_args *args, mrec_stream stream);
 mrec_status mrec_autoint_bwd(const mrec_autoint_args *args, mrec_stream stream);
+
+/* ------------------------------------------------------------------------- */
+/* DIEN interest evolution: interest-extractor GRU, attention, AUGRU, one       */
+/* launch each way (ABI 41; csrc/augru.hip)                                    */
+/* ------------------------------------------------------------------------- */
+/*
+ * Per sample b, for t = 0 .. his_len[b] - 1, both states starting at 0:
+ *   layer 1   h1_t = GRU1(x_t, h1_{t-1})                 mrec_gru's equations, unchanged
+ *   scores    s_t  = h1_t . p[b]       a = softmax of s over t < his_len[b]
+ *                                      (fp32, shifted by the sample's own maximum)
+ *   layer 2   (AUGRU) input i_t = bf16(h1_t); r, z, n as a GRU on (i_t, h2_{t-1})
+ *             u_t  = a_t (1 - z_t)                       the attention scales the update gate
+ *             h2_t = h2_{t-1} + u_t (n_t - h2_{t-1})
+ *   outputs   v[b] = h2_{his_len[b] - 1};  hs1[b, t] = h1_t, zero at t >= his_len[b]
+ * x, the four weight matrices and h as a product's operand are rounded to bf16, every
+ * product accumulates in fp32; the gate math, the carried states, the scores (on the fp32
+ * h1) and the softmax are fp32.  A position is live iff t < his_len[b]; x at other
+ * positions is never read.
+ *   x       bf16 rows [batch * L], row stride ld_x elements (16-byte aligned rows);
+ *   his_len, order, d_oob_flag: as mrec_gru_args (a length outside 1 .. L sets the flag and
+ *           is clamped into 0 .. L; 0 gives v = 0; order changes speed only);
+ *   p       the attention query [batch, H] fp32, row stride ld_p;
+ *   w_ih1 [3H, E], w_hh1 [3H, H], b_ih1, b_hh1 [3H]; w_ih2 [3H, H], w_hh2 [3H, H], b_ih2,
+ *           b_hh2 [3H]: the fp32 masters in nn.GRU's layout, gate order r, z, n;
+ *   hs1, hs2 [batch, L, H] fp32 and att [batch, L] fp32: written by the forward (hs1 in
+ *           full; hs2 at live positions), read by the backward, which recomputes the gates;
+ *   v       [batch, H] fp32 (forward).
+ * Backward: dv [batch, H] fp32 and d_hs1 [batch, L, H] fp32 (NULL: zero; never read at
+ * t >= his_len) give
+ *   dx      bf16 rows (row stride ld_dx), bitwise zero at t >= his_len;
+ *   dp      [batch, H] fp32 (row stride ld_dp);
+ *   part    [parts][mrec_interest_param_count] fp32 per-workgroup partials, flat
+ *           [dW_ih1 | dW_hh1 | db_ih1 | db_hh1 | dW_ih2 | dW_hh2 | db_ih2 | db_hh2]
+ *           (parts = mrec_interest_parts(batch)), to be summed in workgroup order by
+ *           mrec_sasrec_wgrad;
+ *   with    da_t = sum_units dh2_t (1 - z_t)(n_t - h2_{t-1}),  ds_t = a_t (da_t - sum_t' a_t' da_t'),
+ *           dp = sum_t ds_t h1_t, and layer 1 receiving d_hs1[t] + ds_t p + dGx2_t W_ih2 at
+ *           every step.
+ * workspace [batch, L, H] fp32 is the backward's scratch (dGx2 W_ih2), supplied by the
+ * caller.  No atomics: a sample's results depend on that sample alone and every output has
+ * equal bits from run to run.
+ * Compiled shapes (mrec_interest_supported): E, H in {16, 32, 64}, 1 <= L <= 64.  A
+ * workgroup takes mrec_interest_tile() samples at a time.  Stream-ordered, no allocation;
+ * anything else is MREC_EINVAL before any device work.
+ */
+typedef struct {
+  const void *x;
+  int64_t ld_x;
+  const int32_t *his_len;
+  const int32_t *order;
+  const float *p;
+  int64_t ld_p;
+  const float *w_ih1;
+  int64_t ld_ih1;
+  const float *w_hh1;
+  int64_t ld_hh1;
+  const float *b_ih1;
+  const float *b_hh1;
+  const float *w_ih2;
+  int64_t ld_ih2;
+  const float *w_hh2;
+  int64_t ld_hh2;
+  const float *b_ih2;
+  const float *b_hh2;
+  int32_t E;
+  int32_t H;
+  int32_t L;
+  int64_t batch;
+  float *hs1;
+  float *hs2;
+  float *att;
+  float *v;
+  int32_t *d_oob_flag;
+  const float *dv;
+  const float *d_hs1;
+  float *workspace;
+  void *dx;
+  int64_t ld_dx;
+  float *dp;
+  int64_t ld_dp;
+  float *part;
+  int64_t parts;
+} mrec_interest_args;
+
+int32_t mrec_interest_supported(int32_t E, int32_t H, int32_t L);
+int32_t mrec_interest_tile(void);
+int64_t mrec_interest_parts(int64_t batch);
+int64_t mrec_interest_param_count(int32_t E, int32_t H);
+mrec_status mrec_interest_fwd(const mrec_interest_args *args, mrec_stream stream);
+mrec_status mrec_interest_bwd(const mrec_interest_args *args, mrec_stream stream);
 
 #ifdef __cplusplus
 }

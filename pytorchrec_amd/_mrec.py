@@ -20,7 +20,7 @@ import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("MREC_LIB_PATH") or os.path.join(LIB_DIR, "libmrec.so")
 
-ABI_VERSION = 40
+ABI_VERSION = 41
 MAX_TABLES = 64
 BWD_MAX_BATCH = 8192
 BWD_HASH_MAX_BATCH = 4096  # batches up to this use the hash plan (fusable into a GEMM launch)
@@ -356,6 +356,28 @@ class AutoIntArgs(ctypes.Structure):
                 ("workspace_bytes", ctypes.c_int64)]
 
 
+class InterestArgs(ctypes.Structure):
+    """mrec_interest_args (include/mrec.h, ABI 41): one description for both directions."""
+    _fields_ = [("x", ctypes.c_void_p), ("ld_x", ctypes.c_int64),
+                ("his_len", ctypes.c_void_p), ("order", ctypes.c_void_p),
+                ("p", ctypes.c_void_p), ("ld_p", ctypes.c_int64),
+                ("w_ih1", ctypes.c_void_p), ("ld_ih1", ctypes.c_int64),
+                ("w_hh1", ctypes.c_void_p), ("ld_hh1", ctypes.c_int64),
+                ("b_ih1", ctypes.c_void_p), ("b_hh1", ctypes.c_void_p),
+                ("w_ih2", ctypes.c_void_p), ("ld_ih2", ctypes.c_int64),
+                ("w_hh2", ctypes.c_void_p), ("ld_hh2", ctypes.c_int64),
+                ("b_ih2", ctypes.c_void_p), ("b_hh2", ctypes.c_void_p),
+                ("E", ctypes.c_int32), ("H", ctypes.c_int32), ("L", ctypes.c_int32),
+                ("batch", ctypes.c_int64),
+                ("hs1", ctypes.c_void_p), ("hs2", ctypes.c_void_p), ("att", ctypes.c_void_p),
+                ("v", ctypes.c_void_p), ("d_oob_flag", ctypes.c_void_p),
+                ("dv", ctypes.c_void_p), ("d_hs1", ctypes.c_void_p),
+                ("workspace", ctypes.c_void_p),
+                ("dx", ctypes.c_void_p), ("ld_dx", ctypes.c_int64),
+                ("dp", ctypes.c_void_p), ("ld_dp", ctypes.c_int64),
+                ("part", ctypes.c_void_p), ("parts", ctypes.c_int64)]
+
+
 LAYOUT_ROW, LAYOUT_COL = 0, 1
 ACT_NONE, ACT_RELU = 0, 1
 
@@ -582,6 +604,12 @@ SIGNATURES = {
     "mrec_autoint_bwd_workspace_size": (ctypes.c_int64, [_i64, _i32, _i32]),
     "mrec_autoint_fwd": (ctypes.c_int, [ctypes.POINTER(AutoIntArgs), _vp]),
     "mrec_autoint_bwd": (ctypes.c_int, [ctypes.POINTER(AutoIntArgs), _vp]),
+    "mrec_interest_supported": (ctypes.c_int32, [_i32, _i32, _i32]),
+    "mrec_interest_tile": (ctypes.c_int32, []),
+    "mrec_interest_parts": (ctypes.c_int64, [_i64]),
+    "mrec_interest_param_count": (ctypes.c_int64, [_i32, _i32]),
+    "mrec_interest_fwd": (ctypes.c_int, [ctypes.POINTER(InterestArgs), _vp]),
+    "mrec_interest_bwd": (ctypes.c_int, [ctypes.POINTER(InterestArgs), _vp]),
     "mrec_tower_fwd_bwd": (ctypes.c_int, [ctypes.POINTER(TowerArgs), _vp]),
     "mrec_tower_image_elems": (ctypes.c_int64, [_i64, _i64, _i32]),
     "mrec_tower_weight_prep": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),

@@ -234,6 +234,62 @@ def gru_encode(rows: torch.Tensor, his_len: torch.Tensor, w_ih, w_hh, b_ih, b_hh
     return h
 
 
+def interest_evolution(x: torch.Tensor, his_len: torch.Tensor, p: torch.Tensor, w_ih1, w_hh1, b_ih1,
+                       b_hh1, w_ih2, w_hh2, b_ih2, b_hh2, rnd=None, check: bool = True):
+    """DIEN's interest evolution (Zhou et al., AAAI 2019) in torch ops, in the parameters'
+    dtype (fp32, or fp64 as the tests' reference); autograd is its backward.
+
+    x [B, L, E] behaviour rows, his_len [B] in 1..L, p [B, H] the attention query ->
+    (v [B, H], hs1 [B, L, H]).  Per sample, t < his_len, both states starting at 0:
+        h1_t = GRU1(x_t, h1_{t-1})                        (``gru_encode``'s equations)
+        s_t  = h1_t . p;   a = softmax of s over t < his_len
+        r, z, n as a GRU on (h1_t, h2_{t-1});  u_t = a_t (1 - z_t)
+        h2_t = h2_{t-1} + u_t (n_t - h2_{t-1})
+    v = h2_{his_len - 1}; hs1 is zero at t >= his_len.  x at t >= his_len never matters.  A
+    length outside 1..L is IndexError; with ``check`` off, 0 gives v = 0 and more than L
+    runs L steps.
+
+    ``rnd`` rounds x, the four weight matrices, and h1 / h2 as matmul operands (identity
+    here; ``bf16_round`` on a GPU, where this is the layered path whose rounding points are
+    the fused kernel's: the scores use the unrounded h1)."""
+    r_ = rnd if rnd is not None else (lambda t: t)
+    B, L, E = x.shape
+    H = w_hh1.shape[1]
+    dt = w_ih1.dtype
+    lens = his_len.reshape(-1).long()
+    if check and B and (int(lens.min()) < 1 or int(lens.max()) > L):
+        raise IndexError("index out of range in self")
+    live = torch.arange(L, device=x.device).unsqueeze(0) < lens.unsqueeze(1)  # [B, L]
+    # dead rows never matter (they may hold anything, NaN included)
+    xs = r_(torch.where(live.unsqueeze(-1), x.to(dt), torch.zeros((), dtype=dt, device=x.device)))
+    p = p.to(dt)
+
+    def layer(inp, w_ih, w_hh, b_ih, b_hh, att):
+        wi, wh = r_(w_ih), r_(w_hh)
+        gx = inp @ wi.t() + b_ih  # [B, L, 3H]: the input products do not depend on h
+        h = torch.zeros(B, H, dtype=dt, device=x.device)
+        out = []
+        for t in range(L):
+            gh = r_(h) @ wh.t() + b_hh
+            xr, xz, xn = gx[:, t].split(H, dim=1)
+            hr, hz, hn = gh.split(H, dim=1)
+            r = torch.sigmoid(xr + hr)
+            z = torch.sigmoid(xz + hz)
+            n = torch.tanh(xn + r * hn)
+            new = (1.0 - z) * n + z * h if att is None else h + att[:, t:t + 1] * (1.0 - z) * (n - h)
+            h = torch.where(live[:, t:t + 1], new, h)
+            out.append(h)
+        return h, torch.stack(out, dim=1)
+
+    _, hs1 = layer(xs, w_ih1, w_hh1, b_ih1, b_hh1, None)
+    hs1 = hs1 * live.unsqueeze(-1).to(dt)
+    s = (hs1 * p.unsqueeze(1)).sum(-1).masked_fill(~live, float("-inf"))
+    a = torch.softmax(s, dim=1)
+    a = torch.where(live, a, torch.zeros((), dtype=dt, device=x.device))  # (length 0: no NaN)
+    v, _ = layer(r_(hs1), w_ih2, w_hh2, b_ih2, b_hh2, a)
+    return v, hs1
+
+
 def ncf_score(rows: torch.Tensor, E: int, weights, biases, wp, rnd=None, dropout: float = 0.0,
               training: bool = False) -> torch.Tensor:
     """The NCF / NeuMF pair scorer (NCF.py:62-74) in fp32 torch ops; autograd is its

@@ -1177,6 +1177,112 @@ def gru_encode(rows: torch.Tensor, his_len: torch.Tensor, model, order="auto") -
                                rnd=cpu_path.bf16_round if rows.is_cuda else None, check=check)
 
 
+# the fused DIEN interest evolution (mrec_interest_*, augru.hip) is the default for the
+# compiled shapes; False selects the layered path (the parity tests and the benchmark set it)
+DIEN_FUSED = True
+
+
+def interest_supported(E: int, H: int, L: int) -> bool:
+    """True when the fused interest evolution covers (E, H, L).  Decided from the shape
+    alone; never an error."""
+    return bool(_mrec.lib().mrec_interest_supported(int(E), int(H), int(L)))
+
+
+class _InterestFn(torch.autograd.Function):
+    """GRU1 -> attention -> AUGRU over the behaviour rows [B, L, E]: one forward launch
+    (-> v [B, H] and hs1 [B, L, H]; hs2 and the attention weights saved), one backward
+    launch (dx bf16, dp, per-workgroup partials of the eight dense gradients) and the
+    partials' fixed-order sum (mrec_sasrec_wgrad, which is shape-agnostic)."""
+
+    @staticmethod
+    def forward(ctx, x, his_len, p, order, check: bool, *params):
+        B, L, E = x.shape
+        H = params[1].shape[1]
+        dev = x.device
+        x2 = _bf16_rows(x.reshape(B * L, E))
+        his_len = his_len.reshape(-1).to(torch.int32).contiguous()
+        if order is not None:
+            order = order.reshape(-1).to(torch.int32).contiguous()
+        pq = _f32c(p)
+        ws = [_weight_f32(params[0]), _weight_f32(params[1]), _f32c(params[2]), _f32c(params[3]),
+              _weight_f32(params[4]), _weight_f32(params[5]), _f32c(params[6]), _f32c(params[7])]
+        hs1 = torch.empty(B, L, H, dtype=torch.float32, device=dev)
+        hs2 = torch.empty(B, L, H, dtype=torch.float32, device=dev)
+        att = torch.empty(B, L, dtype=torch.float32, device=dev)
+        v = torch.empty(B, H, dtype=torch.float32, device=dev)
+        flag = torch.zeros(1, dtype=torch.int32, device=dev) if check else None
+        a = _mrec.InterestArgs(
+            x2.data_ptr(), x2.stride(0), his_len.data_ptr(), _mrec.ptr(order),
+            pq.data_ptr(), pq.stride(0),
+            ws[0].data_ptr(), ws[0].stride(0), ws[1].data_ptr(), ws[1].stride(0),
+            ws[2].data_ptr(), ws[3].data_ptr(),
+            ws[4].data_ptr(), ws[4].stride(0), ws[5].data_ptr(), ws[5].stride(0),
+            ws[6].data_ptr(), ws[7].data_ptr(), E, H, L, B,
+            hs1.data_ptr(), hs2.data_ptr(), att.data_ptr(), v.data_ptr(), _mrec.ptr(flag),
+            None, None, None, None, 0, None, 0, None, 0)
+        if B:
+            _mrec.call("mrec_interest_fwd", ctypes.byref(a), _mrec.stream_handle())
+        if flag is not None and int(flag.item()) != 0:
+            raise IndexError("index out of range in self")
+        a.d_oob_flag = None
+        ctx.args, ctx.keep = a, (x2, his_len, order, pq, ws, hs1, hs2, att)
+        ctx.att = att  # the attention weights a [B, L], zero at t >= his_len
+        ctx.params = params
+        ctx.set_materialize_grads(False)  # an unused hs1 sends no d_hs1 (NULL: zero)
+        return v, hs1
+
+    @staticmethod
+    def backward(ctx, dv, d_hs1):
+        a, keep = ctx.args, ctx.keep
+        params = ctx.params
+        B, L, E, H = int(a.batch), int(a.L), int(a.E), int(a.H)
+        dev = keep[0].device
+        dv = (torch.zeros(B, H, dtype=torch.float32, device=dev) if dv is None
+              else dv.detach().float().contiguous())
+        if d_hs1 is not None:
+            d_hs1 = d_hs1.detach().float().contiguous()
+        dx = torch.empty(B * L, E, dtype=_BF16, device=dev)
+        dp = torch.empty(B, H, dtype=torch.float32, device=dev)
+        work = torch.empty(B, L, H, dtype=torch.float32, device=dev)
+        a.dv, a.d_hs1, a.workspace = dv.data_ptr(), _mrec.ptr(d_hs1), work.data_ptr()
+        a.dx, a.ld_dx, a.dp, a.ld_dp = dx.data_ptr(), dx.stride(0), dp.data_ptr(), dp.stride(0)
+        lib = _mrec.lib()
+        grads = _sum_partials("mrec_interest_bwd", a, B, int(lib.mrec_interest_parts(B)),
+                              int(lib.mrec_interest_param_count(E, H)),
+                              [3 * H * E, 3 * H * H, 3 * H, 3 * H, 3 * H * H, 3 * H * H, 3 * H, 3 * H],
+                              params, dev)
+        ctx.args = ctx.keep = ctx.att = None
+        return (dx.reshape(B, L, E), None, dp, None, None) + grads
+
+
+def interest_evolution(x: torch.Tensor, his_len: torch.Tensor, p: torch.Tensor, params, order="auto",
+                       check: bool = True):
+    """(v [B, H], hs1 [B, L, H]), both fp32: DIEN's interest extractor GRU, the attention
+    of its states against the query ``p`` [B, H], and the AUGRU, over the behaviour rows
+    ``x`` [B, L, E] (``cpu_path.interest_evolution`` states the arithmetic).  ``params`` =
+    (w_ih1, w_hh1, b_ih1, b_hh1, w_ih2, w_hh2, b_ih2, b_hh2) in nn.GRU's layout.  On a GPU
+    the fused kernels (mrec_interest_fwd / _bwd) when they cover the shape; else, on the CPU
+    and with ``DIEN_FUSED`` off, the layered path: the same arithmetic as torch ops,
+    rounding to bf16 on a GPU where the kernel does.  ``order`` as in ``gru_encode``: it
+    changes speed only."""
+    from pytorchrec_amd import cpu_path
+    B, L, E = x.shape
+    params = tuple(params)
+    if (x.is_cuda and DIEN_FUSED and interest_supported(E, params[1].shape[1], L)
+            and all(w.dtype == torch.float32 for w in params)):
+        if isinstance(order, str):
+            if order not in ("auto", "sorted"):
+                raise ValueError(f"order must be 'auto', 'sorted', None or a permutation: {order}")
+            lib = _mrec.lib()
+            if order == "sorted" or B > int(lib.mrec_interest_parts(B)) * int(lib.mrec_interest_tile()):
+                order = torch.argsort(his_len.reshape(-1), descending=True, stable=True)
+            else:
+                order = None
+        return _InterestFn.apply(x, his_len, p, order, check, *params)
+    return cpu_path.interest_evolution(x, his_len, p, *params,
+                                       rnd=cpu_path.bf16_round if x.is_cuda else None, check=check)
+
+
 # the fused NCF pair scorer (mrec_ncf_*, ncf.hip) is the default for the compiled shapes;
 # False selects the layered path (the parity tests and the benchmark set it)
 NCF_FUSED = True

@@ -7,6 +7,7 @@ from pytorchrec_amd.model.DIN import DIN
 from pytorchrec_amd.model.DLRM import DLRM
 from pytorchrec_amd.model.FunkSVD import FunkSVD
 from pytorchrec_amd.model.GRU4Rec import GRU4Rec
+from pytorchrec_amd.model.DIEN import DIEN
 from pytorchrec_amd.model.IModel import IModel
 from pytorchrec_amd.model.NCF import NCF
 from pytorchrec_amd.model.SASRec import SASRec
@@ -24,6 +25,7 @@ _model_classes: Dict[str, Type[IModel]] = {
     "deepfm": DeepFM,
     "dcnv2": DCNv2,
     "din": DIN,
+    "dien": DIEN,
     "dlrm": DLRM,
     "xdeepfm": XDeepFM,
     "autoint": AutoInt,
