@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MREC_ABI_VERSION 41
+#define MREC_ABI_VERSION 42
 #define MREC_MAX_TABLES 64      /* tables per table bank / per call */
 #define MREC_BWD_MAX_BATCH 8192  /* lookups per table per plan/apply call */
 #define MREC_BWD_HASH_MAX_BATCH 4096  /* batches up to this use the hash plan */
@@ -2223,6 +2223,91 @@ int64_t mrec_interest_parts(int64_t batch);
 int64_t mrec_interest_param_count(int32_t E, int32_t H);
 mrec_status mrec_interest_fwd(const mrec_interest_args *args, mrec_stream stream);
 mrec_status mrec_interest_bwd(const mrec_interest_args *args, mrec_stream stream);
+
+/* ------------------------------------------------------------------------- */
+/* DCN-Mix: a stack of low-rank mixture-of-experts cross layers, one launch     */
+/* each way (ABI 42; csrc/cross_mix.hip)                                       */
+/* ------------------------------------------------------------------------- */
+/*
+ * Per layer, with K experts of rank r over d columns: V [K r, d], C [K, r, r], U [d, K r],
+ * b [d], gate [K, d] (no gate when K = 1).  Every product's operands are bf16 (RNE),
+ * accumulation is fp32:
+ *   x_0     = bf16(x0)
+ *   t_i     = V_i x_l                    a_i = bf16(tanh(t_i))          i = 1 .. K
+ *   c_i     = bf16(tanh(C_i a_i))
+ *   gamma   = softmax_i(gate_i . x_l)    fp32, shifted by the maximum; K = 1: gamma = 1
+ *   s_i     = bf16(gamma_i c_i)
+ *   z       = U [s_1 | .. | s_K] + b     fp32
+ *   x_{l+1} = bf16(x0 * z + x_l)
+ * tanh(x) = 1 - 2 / (1 + exp(2 x)) with 1-ulp exp and reciprocal.  y = x_L [batch, d] bf16.
+ *   x0      [batch, d] MREC_F32 or MREC_BF16, 16-byte aligned rows of at least round8(d)
+ *           elements; columns d .. round8(d) may hold anything and count as zero;
+ *   w_img[l] one bf16 image per layer, mrec_cross_mix_image_elems(d, K, r) elements, built by
+ *           the caller whenever a weight changes.  With dk = round32(d), d16 = round16(d), n1 =
+ *           K r (+ 16 when K > 1), n1k = round32(n1), krk = round32(K r), rk = max(r, 32), it
+ *           holds six row-major matrices one after the other, every pad element zero:
+ *             vg  [n1][dk]    rows V, then gate      vgT [d16][n1k]  vg's transpose
+ *             u   [d16][krk]  U                      uT  [K r][dk]   U's transpose
+ *             c   [K r][rk]   row i r + j = C_i[j]   cT  [K r][rk]   row i r + j = C_i[:, j]
+ *   bias[l] b, fp32 [d];
+ *   train   != 0: the forward also writes every layer's input x_l to saved [layers][batch]
+ *           [ld_saved] bf16 (layer stride saved_layer_stride elements, rows of round8(d)
+ *           elements with zero pad columns).  The forward writes nothing else.
+ * Backward (mrec_cross_mix_bwd; reads saved, the images, bias and dy [batch, d] MREC_F32 or
+ * MREC_BF16, rows as x0's): with g = dL/dx_{l+1} (bf16 between the layers), top layer first,
+ *   dz = bf16(g x_0)      dx0 += g z (fp32)      ds = U^T dz      e_i = ds_i . c_i
+ *   dlogit_i = bf16(gamma_i (e_i - sum_j gamma_j e_j))
+ *   du_i = bf16(gamma_i ds_i (1 - c_i^2))        dt_i = bf16((C_i^T du_i)(1 - a_i^2))
+ *   dx_l = g + V^T dt + gate^T dlogit            layer 0's joins dx0
+ * a, c, gamma, s and z are recomputed from saved with the forward's code.  dx0 [batch, d]
+ * fp32 (row stride ld_dx0) is overwritten.  The operands of the weight gradients go to the
+ * workspace (16-byte aligned, mrec_cross_mix_bwd_workspace_size bytes) in bf16, pad columns
+ * zero, as five arrays one after the other, each [layers][batch][width]:
+ *   dz [round8(d)]   s [K r]   du [K r]   a [K r]   dtl = [dt | dlogit | 0] [n1]
+ * so that  dU = dz^T s,  db = sum_b dz,  dC_i = du_i^T a_i,  [dV ; dgate] = dtl^T x_l  are
+ * plain GEMMs over the batch (mrec_gemm).
+ *   Determinism: no atomics; a sample's results depend on that sample alone and every output
+ * has equal bits from run to run.  A workgroup takes 16 samples at a time.
+ * Compiled shapes (mrec_cross_mix_supported, decided from the shape alone): 1 <= d <= 512,
+ * r in {16, 32, 64}, 1 <= K <= 4 with K r <= 256, 1 <= layers <= 4.  batch = 0 launches
+ * nothing.  Stream-ordered, no allocation; anything else is MREC_EINVAL with
+ * mrec_last_error() before any launch.  One description for both directions: the forward
+ * ignores dy, dx0 and the workspace, the backward x0 and y.
+ */
+#define MREC_CROSS_MIX_MAX_LAYERS 4
+
+typedef struct {
+  const void *x0;
+  mrec_dtype x0_dtype;
+  int64_t ld_x0;
+  const void *w_img[MREC_CROSS_MIX_MAX_LAYERS];
+  const float *bias[MREC_CROSS_MIX_MAX_LAYERS];
+  int64_t batch;
+  int32_t d;
+  int32_t K;
+  int32_t r;
+  int32_t layers;
+  int32_t train;
+  void *y;
+  int64_t ld_y;
+  void *saved; /* written by a training forward, read by the backward */
+  int64_t ld_saved;
+  int64_t saved_layer_stride;
+  const void *dy;
+  mrec_dtype dy_dtype;
+  int64_t ld_dy;
+  float *dx0;
+  int64_t ld_dx0;
+  void *workspace;
+  int64_t workspace_bytes;
+} mrec_cross_mix_args;
+
+int32_t mrec_cross_mix_supported(int32_t d, int32_t K, int32_t r, int32_t layers);
+int64_t mrec_cross_mix_image_elems(int32_t d, int32_t K, int32_t r);
+int64_t mrec_cross_mix_bwd_workspace_size(int64_t batch, int32_t d, int32_t K, int32_t r,
+                                          int32_t layers);
+mrec_status mrec_cross_mix_fwd(const mrec_cross_mix_args *args, mrec_stream stream);
+mrec_status mrec_cross_mix_bwd(const mrec_cross_mix_args *args, mrec_stream stream);
 
 #ifdef __cplusplus
 }

@@ -20,7 +20,7 @@ import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("MREC_LIB_PATH") or os.path.join(LIB_DIR, "libmrec.so")
 
-ABI_VERSION = 41
+ABI_VERSION = 42
 MAX_TABLES = 64
 BWD_MAX_BATCH = 8192
 BWD_HASH_MAX_BATCH = 4096  # batches up to this use the hash plan (fusable into a GEMM launch)
@@ -378,6 +378,25 @@ class InterestArgs(ctypes.Structure):
                 ("part", ctypes.c_void_p), ("parts", ctypes.c_int64)]
 
 
+CROSS_MIX_MAX_LAYERS = 4
+
+
+class CrossMixArgs(ctypes.Structure):
+    """mrec_cross_mix_args (include/mrec.h, ABI 42): the DCN-Mix cross stack, both directions."""
+    _fields_ = [("x0", ctypes.c_void_p), ("x0_dtype", ctypes.c_int), ("ld_x0", ctypes.c_int64),
+                ("w_img", ctypes.c_void_p * CROSS_MIX_MAX_LAYERS),
+                ("bias", ctypes.c_void_p * CROSS_MIX_MAX_LAYERS),
+                ("batch", ctypes.c_int64),
+                ("d", ctypes.c_int32), ("K", ctypes.c_int32), ("r", ctypes.c_int32),
+                ("layers", ctypes.c_int32), ("train", ctypes.c_int32),
+                ("y", ctypes.c_void_p), ("ld_y", ctypes.c_int64),
+                ("saved", ctypes.c_void_p), ("ld_saved", ctypes.c_int64),
+                ("saved_layer_stride", ctypes.c_int64),
+                ("dy", ctypes.c_void_p), ("dy_dtype", ctypes.c_int), ("ld_dy", ctypes.c_int64),
+                ("dx0", ctypes.c_void_p), ("ld_dx0", ctypes.c_int64),
+                ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64)]
+
+
 LAYOUT_ROW, LAYOUT_COL = 0, 1
 ACT_NONE, ACT_RELU = 0, 1
 
@@ -604,6 +623,11 @@ SIGNATURES = {
     "mrec_autoint_bwd_workspace_size": (ctypes.c_int64, [_i64, _i32, _i32]),
     "mrec_autoint_fwd": (ctypes.c_int, [ctypes.POINTER(AutoIntArgs), _vp]),
     "mrec_autoint_bwd": (ctypes.c_int, [ctypes.POINTER(AutoIntArgs), _vp]),
+    "mrec_cross_mix_supported": (ctypes.c_int32, [_i32, _i32, _i32, _i32]),
+    "mrec_cross_mix_image_elems": (ctypes.c_int64, [_i32, _i32, _i32]),
+    "mrec_cross_mix_bwd_workspace_size": (ctypes.c_int64, [_i64, _i32, _i32, _i32, _i32]),
+    "mrec_cross_mix_fwd": (ctypes.c_int, [ctypes.POINTER(CrossMixArgs), _vp]),
+    "mrec_cross_mix_bwd": (ctypes.c_int, [ctypes.POINTER(CrossMixArgs), _vp]),
     "mrec_interest_supported": (ctypes.c_int32, [_i32, _i32, _i32]),
     "mrec_interest_tile": (ctypes.c_int32, []),
     "mrec_interest_parts": (ctypes.c_int64, [_i64]),

@@ -786,3 +786,82 @@ def autoint(x0, layers, heads: int, scale: float = 1.0, round_bf16: bool = False
     meta = (m, tuple(has_res), heads, float(scale), int(chunk), rnd, store)
     y = _AutoIntFn.apply(x0, meta, *flat)
     return y.to(x_dtype or x0.dtype)
+
+
+def _cross_mix_stack(xc, flat, K, rnd):
+    """All layers on a chunk: xc [b, d] -> x_L [b, d] in xc's arithmetic dtype; ``flat`` holds
+    (V, C, U, b[, gate]) per layer."""
+    r = _ste(rnd)
+    x0 = r(xc)
+    x, n = x0, 5 if K > 1 else 4
+    for k in range(0, len(flat), n):
+        V, C, U, b = flat[k:k + 4]
+        rk = C.shape[1]
+        a = r(torch.tanh(x @ r(V).t())).view(-1, K, rk)
+        c = r(torch.tanh(torch.einsum("bik,ijk->bij", a, r(C))))
+        if K > 1:
+            c = c * torch.softmax(x @ r(flat[k + 4]).t(), dim=-1).unsqueeze(-1)
+        z = r(c).reshape(-1, K * rk) @ r(U).t() + b
+        x = r(x0 * z + x)
+    return x
+
+
+class _CrossMixFn(torch.autograd.Function):
+    """The DCN-Mix stack in torch ops, both directions chunked over the batch; the backward
+    recomputes the forward of its chunk from x0, as the kernel does."""
+
+    @staticmethod
+    def forward(ctx, x0, meta, *flat):
+        K, chunk, rnd = meta
+        dt = torch.float64 if x0.dtype == torch.float64 else torch.float32
+        ws = [w.detach().to(dt) for w in flat]
+        xs = x0.detach().to(dt)
+        with torch.no_grad():
+            ys = [_cross_mix_stack(xs[s:s + chunk], ws, K, rnd) for s in range(0, x0.shape[0], chunk)]
+        ctx.save_for_backward(x0, *flat)
+        ctx.meta = meta
+        return torch.cat(ys) if ys else xs.new_zeros(x0.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x0, *flat = ctx.saved_tensors
+        K, chunk, rnd = ctx.meta
+        dt = torch.float64 if x0.dtype == torch.float64 else torch.float32
+        ws = [w.detach().to(dt).requires_grad_(True) for w in flat]
+        dx = torch.zeros(x0.shape, dtype=dt, device=x0.device)
+        dws = [torch.zeros_like(w) for w in ws]
+        dy = _ste(rnd)(dy.detach().to(dt))
+        for s in range(0, x0.shape[0], chunk):
+            with torch.enable_grad():
+                xc = x0[s:s + chunk].detach().to(dt).requires_grad_(True)
+                gs = torch.autograd.grad(_cross_mix_stack(xc, ws, K, rnd), [xc] + ws, dy[s:s + chunk])
+            dx[s:s + chunk] = gs[0]
+            for a, g in zip(dws, gs[1:]):
+                a += g
+        return (dx.to(x0.dtype), None, *[g.to(w.dtype) for g, w in zip(dws, flat)])
+
+
+def cross_mix(x0, layers, round_bf16: bool = False, chunk: int = 1024):
+    """``mrec_cross_mix_fwd`` / ``_bwd`` in torch ops (include/mrec.h "DCN-Mix"): ``x0 [B, d]``,
+    ``layers[l]`` = ``(V [K r, d], C [K, r, r], U [d, K r], b [d], gate [K, d] or None)``, the
+    gate present iff K > 1 ->  x_L ``[B, d]``:  a_i = tanh(V_i x_l), c_i = tanh(C_i a_i), gamma =
+    softmax(gate x_l), z = U [gamma_i c_i] + b, x_{l+1} = x0 * z + x_l.  Arithmetic in fp32 (fp64
+    operands stay fp64), ``chunk`` samples at a time in both directions.  ``round_bf16`` rounds
+    where the kernel's forward rounds (x0, the matrices, a, c, gamma c, x_{l+1}, dy) and returns
+    bf16: the GPU path of a shape the kernels do not cover, and their comparator."""
+    layers = [tuple(l) for l in layers]
+    if not layers or x0.dim() != 2:
+        raise ValueError("cross_mix needs x0 [B, d] and at least one layer")
+    d = x0.shape[1]
+    K, r = layers[0][1].shape[0], layers[0][1].shape[1]
+    flat = []
+    for l in layers:
+        if len(l) != 5 or (l[4] is None) != (K == 1):
+            raise ValueError("a layer is (V, C, U, b, gate), gate None iff there is one expert")
+        want = ((K * r, d), (K, r, r), (d, K * r), (d,), (K, d))
+        for w, shape in zip(l, want):
+            if w is not None and tuple(w.shape) != shape:
+                raise ValueError(f"DCN-Mix parameter must be {shape}, got {tuple(w.shape)}")
+        flat += [w for w in l if w is not None]
+    y = _CrossMixFn.apply(x0, (K, int(chunk), bf16_round_any if round_bf16 else None), *flat)
+    return y.to(torch.bfloat16) if round_bf16 else y

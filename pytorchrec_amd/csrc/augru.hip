@@ -108,9 +108,6 @@ constexpr float AU_LOG2E = 1.4426950408889634f;
 __device__ __forceinline__ float au_sigmoid(float x) {
   return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-AU_LOG2E * x));
 }
-__device__ __forceinline__ float au_tanh(float x) {
-  return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(2.f * AU_LOG2E * x));
-}
 
 // sum over the 16 lanes of this lane's DPP row (every lane gets it; a fixed tree)
 __device__ __forceinline__ float au_row_sum(float v) {
@@ -283,7 +280,7 @@ __device__ __forceinline__ void au_recur_fwd(const AuArgs &p, AuLayer w, uint16_
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float r = au_sigmoid(ar[e] + br), z = au_sigmoid(az[e] + bz);
-      const float n = au_tanh(anx[e] + bnx + r * (anh[e] + bnh));
+      const float n = tanh_rcp(anx[e] + bnx + r * (anh[e] + bnh));
       const bool live = t < lenC[e];
       if constexpr (ATT) {
         const float ug = s_att[(4 * q + e) * AU_LS + t] * (1.f - z);
@@ -509,7 +506,7 @@ __device__ __forceinline__ void au_recur_bwd(const AuArgs &p, AuLayer w, float *
       const float hp = live && t > 0 ? hs[(baseC[e] + t - 1) * H + u] : 0.f;
       const float r = au_sigmoid(ar[e] + br), z = au_sigmoid(az[e] + bz);
       const float hn = anh[e] + bnh;
-      const float n = au_tanh(anx[e] + bnx + r * hn);
+      const float n = tanh_rcp(anx[e] + bnx + r * hn);
       const float d = live ? dh[e] + ex[e] : 0.f;
       // h_t = h_{t-1} + gn (n - h_{t-1}):  gn = 1 - z (GRU), a_t (1 - z) (AUGRU)
       const float at = ATT ? s_att[(4 * q + e) * AU_LS + t] : 1.f;

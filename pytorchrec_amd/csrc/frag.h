@@ -160,6 +160,15 @@ __device__ __forceinline__ float dsigmoid_stable(float x) {
 }
 
 // ---------------------------------------------------------------------------
+// tanh = 1 - 2 / (1 + exp(2x)) on v_exp_f32 and v_rcp_f32 (1 ulp each): goes to its limits
+// without inf / inf for large |x| (exp -> inf gives rcp -> 0).  A kernel's forward and its
+// recomputing backward share it, so the backward gets the forward's bits.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float tanh_rcp(float x) {
+  return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(2.f * 1.4426950408889634f * x));
+}
+
+// ---------------------------------------------------------------------------
 // host side: the checks and descriptors of a runtime-dtype operand
 // ---------------------------------------------------------------------------
 inline bool is_float_dtype(mrec_dtype t) { return t == MREC_F32 || t == MREC_BF16; }

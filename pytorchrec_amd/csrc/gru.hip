@@ -98,9 +98,6 @@ constexpr float GR_LOG2E = 1.4426950408889634f;
 __device__ __forceinline__ float gr_sigmoid(float x) {
   return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-GR_LOG2E * x));
 }
-__device__ __forceinline__ float gr_tanh(float x) {
-  return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(2.f * GR_LOG2E * x));
-}
 
 // fragment of W[n0 + (lane & 15)][k0 + 8 (lane >> 4) .. + 8] (zero past `cols`): the B
 // operand of a product over W's columns, from the fp32 master
@@ -231,7 +228,7 @@ __global__ __launch_bounds__(64 * (H / 16)) void gru_fwd_kernel(GruArgs p) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float r = gr_sigmoid(ar[e] + br), z = gr_sigmoid(az[e] + bz);
-        const float n = gr_tanh(anx[e] + bnx + r * (anh[e] + bnh));
+        const float n = tanh_rcp(anx[e] + bnx + r * (anh[e] + bnh));
         const bool live = t < lenC[e];
         h[e] = live ? (1.f - z) * n + z * h[e] : h[e];
         if (live) hsC[e][static_cast<int64_t>(t) * H] = h[e];
@@ -377,7 +374,7 @@ __global__ __launch_bounds__(64 * (H / 16)) void gru_bwd_kernel(GruArgs p) {
         const float hp = live && t > 0 ? p.hs[(baseC[e] + t - 1) * H + u] : 0.f;
         const float r = gr_sigmoid(ar[e] + br), z = gr_sigmoid(az[e] + bz);
         const float hn = anh[e] + bnh;
-        const float n = gr_tanh(anx[e] + bnx + r * hn);
+        const float n = tanh_rcp(anx[e] + bnx + r * hn);
         const float d = live ? dh[e] : 0.f;
         const float dan = d * (1.f - z) * (1.f - n * n);
         const float dar = dan * hn * r * (1.f - r);

@@ -1,6 +1,7 @@
 """Dense-tower ops: Linear(+bias)(+ReLU), DCN-v2 cross, DIN attention pooling, the
 SASRec / GRU4Rec encoders, the NCF scorer, DLRM's pairwise dot interaction, xDeepFM's
-Compressed Interaction Network, AutoInt's interacting (field self-attention) layers.
+Compressed Interaction Network, AutoInt's interacting (field self-attention) layers, DCN-v2's
+low-rank mixture-of-experts cross stack.
 
 One seam for the model code.  On a GPU they run on libmrec's MFMA bf16 GEMM
 (``mrec_gemm``: fp32 accumulation, bias / ReLU / DCN epilogues fused, the fp32
@@ -311,12 +312,14 @@ def weight_prep(W: torch.Tensor, row: bool = True, tr: bool = True):
 #   "cin":   the forward and transposed images of a CIN layer (mrec_cin_fwd / _bwd);
 #   "autoint": the [Wres | Wq | Wk | Wv] image of an AutoInt layer and its transpose, kept on
 #            Wq (mrec_autoint_fwd / _bwd).
+#   "cross_mix": the six matrices of a DCN-Mix layer in one buffer, kept on V
+#            (mrec_cross_mix_fwd / _bwd).
 # An entry is valid while (weight._version, weight._mrec_gen) is unchanged: torch
 # modifying the weight bumps the version; a kernel updating it in place (fused
 # SGD) re-emits the images it was handed and ``images_updated`` bumps the
 # generation and re-stamps that kind, so only the other kind goes stale.
 _IMG_ATTR = {"rowtr": "_mrec_img", "tower": "_mrec_timg", "cin": "_mrec_cimg",
-             "autoint": "_mrec_aimg"}
+             "autoint": "_mrec_aimg", "cross_mix": "_mrec_ximg"}
 
 
 def _img_state(weight):
@@ -1768,6 +1771,208 @@ def autoint(x0: torch.Tensor, n_fields: int, layers, heads: int, scale: float = 
             flat = [w for l in layers for w in l if w is not None]
             return _AutoIntFn.apply(x0, m, heads, float(scale), x_dtype, has_res, *flat)
     return cpu_path.autoint(x0, layers, heads, scale, round_bf16=x0.is_cuda, x_dtype=x_dtype)
+
+
+# the fused DCN-Mix cross stack (mrec_cross_mix_fwd / _bwd, cross_mix.hip) is the default for
+# the compiled shapes; False selects the torch-ops path (the parity tests and the benchmark
+# set it)
+CROSS_MIX_FUSED = True
+
+
+def cross_mix_supported(d: int, K: int, r: int, layers: int, x0_dtype=torch.float32) -> bool:
+    """True when the fused DCN-Mix stack covers d columns, K experts of rank r, the number of
+    layers and x0's dtype.  Decided from the shape alone; never an error."""
+    return (x0_dtype in _DI_DTYPES
+            and bool(_mrec.lib().mrec_cross_mix_supported(int(d), int(K), int(r), int(layers))))
+
+
+def _r(n: int, m: int) -> int:
+    return (n + m - 1) // m * m
+
+
+def _cross_mix_views(buf, d: int, K: int, r: int):
+    """The six matrices of a layer's image buffer (include/mrec.h "DCN-Mix"), as views."""
+    kr = K * r
+    n1 = kr + (16 if K > 1 else 0)
+    shapes = ((n1, _r(d, 32)), (_r(d, 16), _r(n1, 32)), (_r(d, 16), _r(kr, 32)), (kr, _r(d, 32)),
+              (kr, max(r, 32)), (kr, max(r, 32)))
+    out, o = [], 0
+    for rows, cols in shapes:
+        out.append(buf[o:o + rows * cols].view(rows, cols))
+        o += rows * cols
+    return out
+
+
+def cross_mix_images(V, C, U, gate):
+    """The bf16 image of one DCN-Mix layer (zeros in every pad), cached on V like
+    ``weight_images`` and valid while none of the four matrices changed -> (buffer, views)."""
+    key = tuple(_img_state(w) for w in (V, C, U, gate) if w is not None)
+    c = getattr(V, _IMG_ATTR["cross_mix"], None)
+    if c is not None and c[0] == key and c[1].device == V.device:
+        return c[1], c[2]
+    K, r = C.shape[0], C.shape[1]
+    d, kr = V.shape[1], K * r
+    buf = torch.zeros(int(_mrec.lib().mrec_cross_mix_image_elems(d, K, r)), dtype=_BF16, device=V.device)
+    vg, vgT, u, uT, c_, cT = views = _cross_mix_views(buf, d, K, r)
+    with torch.no_grad():
+        vg[:kr, :d] = V
+        vgT[:d, :kr] = V.t()
+        if gate is not None:
+            vg[kr:kr + K, :d] = gate
+            vgT[:d, kr:kr + K] = gate.t()
+        u[:d, :kr] = U
+        uT[:, :d] = U.t()
+        c_[:, :r] = C.reshape(kr, r)
+        cT[:, :r] = C.transpose(1, 2).reshape(kr, r)
+    setattr(V, _IMG_ATTR["cross_mix"], (key, buf, views))
+    return buf, views
+
+
+def _cross_mix_dest(W, b, lr, img_row, img_tr) -> _GradDest:
+    """``_grad_dest`` for a matrix whose images are blocks of a DCN-Mix layer image: fused SGD
+    (which rewrites the blocks) or returned."""
+    if lr is None:
+        return _grad_dest(W, b, None, "rowtr", (None, None))
+    images_updated(W, "rowtr")
+    kw = dict(out=W.detach(), ones_out=None if b is None else b.detach(), out_dtype=torch.float32,
+              sgd_lr=lr, img_row=img_row, img_tr=img_tr, img_kind=_mrec.IMG_ROW_TR)
+    return _GradDest("sgd", kw, None, None)
+
+
+def _cross_mix_rows(t: torch.Tensor) -> torch.Tensor:
+    """``_rows16`` whose rows also hold round8(columns) elements (the kernels load 8 at a time)."""
+    if t.stride(0) >= _r8(t.shape[1]):
+        return _rows16(t)
+    out = _alloc(t.shape[0], t.shape[1], t.dtype, t.device)
+    out.copy_(t)
+    return out
+
+
+class _CrossMixFn(torch.autograd.Function):
+    """The DCN-Mix stack: one forward launch (x_L and, when a gradient is wanted, every layer's
+    input), one backward launch (dx0 and the operands of the weight-gradient products), then
+    per layer dU (+ db as its ones column), dV, dgate and dC_i as GEMMs over the batch, four to
+    a launch (``launch_multi``), whose results go where ``_grad_dest`` says: fused SGD, which
+    rewrites the layer's image in the GEMM's epilogue, or returned."""
+
+    @staticmethod
+    def forward(ctx, x0, K: int, r: int, *flat):
+        B, d = x0.shape
+        dev = x0.device
+        n = 5 if K > 1 else 4
+        layers = [flat[k:k + n] + ((None,) if K == 1 else ()) for k in range(0, len(flat), n)]
+        L = len(layers)
+        x0r = _cross_mix_rows(x0.detach())
+        train = any(ctx.needs_input_grad)
+        a = _mrec.CrossMixArgs()
+        keep = []
+        for l, (V, C, U, b, gate) in enumerate(layers):
+            buf, views = cross_mix_images(V, C, U, gate)
+            bias = _f32c(b)
+            keep.append((buf, views, bias))
+            a.w_img[l], a.bias[l] = buf.data_ptr(), bias.data_ptr()
+        # (x_L's pad columns are read by the next layer's 16-byte staging: they must be zero)
+        y = torch.zeros(B, _r8(d), dtype=_BF16, device=dev)[:, :d] if d % 8 else _alloc(B, d, _BF16, dev)
+        saved = torch.empty(L, B, _r8(d), dtype=_BF16, device=dev) if train else None
+        a.x0, a.x0_dtype, a.ld_x0 = x0r.data_ptr(), _mrec.dtype_code(x0r.dtype), x0r.stride(0)
+        a.batch, a.d, a.K, a.r, a.layers, a.train = B, d, K, r, L, int(train)
+        a.y, a.ld_y = y.data_ptr(), y.stride(0)
+        if train:
+            a.saved, a.ld_saved, a.saved_layer_stride = saved.data_ptr(), saved.stride(1), saved.stride(0)
+        if B:
+            _mrec.call("mrec_cross_mix_fwd", ctypes.byref(a), _mrec.stream_handle())
+        ctx.args, ctx.keep, ctx.layers, ctx.saved = a, keep, layers, saved
+        ctx.x0_dtype = x0.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        a, keep, layers, saved = ctx.args, ctx.keep, ctx.layers, ctx.saved
+        L, B, dp8 = saved.shape
+        d, K, r = int(a.d), int(a.K), int(a.r)
+        kr = K * r
+        n1 = kr + (16 if K > 1 else 0)
+        dev = saved.device
+        if not B:
+            ctx.args = ctx.keep = ctx.layers = ctx.saved = None
+            zeros = [torch.zeros_like(w) for l in layers for w in l if w is not None]
+            return (torch.zeros(0, d, dtype=ctx.x0_dtype, device=dev), None, None, *zeros)
+        dy = dy.detach()
+        if dy.dtype not in _DI_DTYPES:
+            dy = dy.float()
+        dy = _cross_mix_rows(dy)
+        dx0 = torch.empty(B, dp8, dtype=torch.float32, device=dev)[:, :d]
+        nws = int(_mrec.lib().mrec_cross_mix_bwd_workspace_size(B, d, K, r, L))
+        ws = torch.empty(max(nws, 16) // 2, dtype=_BF16, device=dev)
+        a.dy, a.dy_dtype, a.ld_dy = dy.data_ptr(), _mrec.dtype_code(dy.dtype), dy.stride(0)
+        a.dx0, a.ld_dx0 = dx0.data_ptr(), dx0.stride(0)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), nws
+        _mrec.call("mrec_cross_mix_bwd", ctypes.byref(a), _mrec.stream_handle())
+        ops, o = [], 0
+        for w in (dp8, kr, kr, kr, n1):
+            ops.append(ws[o:o + L * B * w].view(L, B, w))
+            o += L * B * w
+        dz, s, du, aa, dtl = ops
+        grads, calls = [], []
+
+        def dw(A, X, dest):  # dest's [N, K] = A^T X over the batch, + the ones column
+            # not split over the batch: four products share a launch, and each split one would
+            # add a deferred reduction to a step the host's issue rate bounds (DCNMix train
+            # step at B = 4096: 1.58 ms unsplit, 1.70 ms split by _split_beside, same host)
+            calls.append(_Call(A, _mrec.LAYOUT_COL, X, _mrec.LAYOUT_COL, A.shape[1], X.shape[1], B,
+                               _mrec.GEMM_FULL, **dest.kw))
+            return dest
+
+        for l, (V, C, U, b, gate) in enumerate(layers):
+            vg, vgT, u, uT, c_, cT = keep[l][1]
+            lr, _ = _decide([w for w in (V, C, U, b, gate) if w is not None], dp=False)
+            xl = saved[l][:, :d]
+            dU = dw(dz[l][:, :d], s[l], _cross_mix_dest(U, b, lr, u[:d, :kr], uT[:, :d]))
+            dV = dw(dtl[l][:, :kr], xl, _cross_mix_dest(V, None, lr, vg[:kr, :d], vgT[:d, :kr]))
+            dC = None if lr is not None else torch.empty(K, r, r, dtype=torch.float32, device=dev)
+            for i in range(K):
+                blk = slice(i * r, (i + 1) * r)
+                dw(du[l][:, blk], aa[l][:, blk],
+                   _cross_mix_dest(C[i], None, lr, c_[blk, :r], cT[blk, :r]) if lr is not None else
+                   _GradDest("ret", dict(out=dC[i], out_dtype=torch.float32), dC[i], None))
+            dg = None
+            if gate is not None:
+                dg = dw(dtl[l][:, kr:kr + K], xl,
+                        _cross_mix_dest(gate, None, lr, vg[kr:kr + K, :d], vgT[:d, kr:kr + K])).dW
+            if lr is not None:  # every matrix of the layer is updated together with its image blocks
+                images_updated(C, "rowtr")
+                key = tuple(_img_state(w) for w in (V, C, U, gate) if w is not None)
+                setattr(V, _IMG_ATTR["cross_mix"], (key,) + keep[l][:2])
+            grads += [dV.dW, dC, dU.dW, dU.db] + ([dg] if K > 1 else [])
+        launch_multi(calls)  # all layers' products, four to a launch
+        ctx.args = ctx.keep = ctx.layers = ctx.saved = None
+        return (dx0.to(ctx.x0_dtype), None, None, *grads)
+
+
+def cross_mix(x0: torch.Tensor, layers) -> torch.Tensor:
+    """DCN-v2's low-rank mixture-of-experts cross stack (include/mrec.h "DCN-Mix"): ``x0 [B, d]``
+    (the interact launch's x0 rows: bf16 or fp32, a column slice of padded rows is fine),
+    ``layers[l]`` = ``(V [K r, d], C [K, r, r], U [d, K r], b [d], gate [K, d] or None)``, the
+    gate present iff K > 1 -> x_L ``[B, d]``, bf16 on a GPU.  On a GPU the fused kernels for the
+    compiled shapes with fp32 parameters; else, and on the CPU, the same contract as torch ops
+    chunked over the batch (``cpu_path.cross_mix``), rounding on a GPU where the kernels round."""
+    from pytorchrec_amd import cpu_path
+    layers = [tuple(l) for l in layers]
+    if x0.dim() != 2 or not layers or any(len(l) != 5 for l in layers):
+        raise ValueError("cross_mix needs x0 [B, d] and layers of (V, C, U, b, gate or None)")
+    if x0.is_cuda and CROSS_MIX_FUSED:
+        d = x0.shape[1]
+        C = layers[0][1]
+        K, r = (C.shape[0], C.shape[1]) if C.dim() == 3 else (0, 0)
+        want = ((K * r, d), (K, r, r), (d, K * r), (d,), (K, d))
+        ok = all((w is None and k == 4 and K == 1) or
+                 (w is not None and tuple(w.shape) == want[k] and w.dtype == torch.float32
+                  and w.is_cuda and w.is_contiguous() and not (k == 4 and K == 1))
+                 for l in layers for k, w in enumerate(l))
+        if ok and cross_mix_supported(d, K, r, len(layers), x0.dtype):
+            flat = [w for l in layers for w in l if w is not None]
+            return _CrossMixFn.apply(x0, K, r, *flat)
+    return cpu_path.cross_mix(x0, layers, round_bf16=x0.is_cuda)
 
 
 def colsum(s: torch.Tensor, X: Optional[torch.Tensor], want_total: bool = True, *,

@@ -2,6 +2,7 @@
 from pytorchrec_amd.model.IModel import IModel
 from pytorchrec_amd.model.DeepFM import FM, DeepFM
 from pytorchrec_amd.model.DCNv2 import DCNv2
+from pytorchrec_amd.model.DCNMix import DCNMix
 from pytorchrec_amd.model.DIN import DIN
 from pytorchrec_amd.model.DLRM import DLRM
 from pytorchrec_amd.model.XDeepFM import XDeepFM

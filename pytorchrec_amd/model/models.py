@@ -1,6 +1,7 @@
 """Model registry — mirror of torchrec/model/models.py:8-30 (the plug-in point)."""
 from typing import Dict, Type
 
+from pytorchrec_amd.model.DCNMix import DCNMix
 from pytorchrec_amd.model.DCNv2 import DCNv2
 from pytorchrec_amd.model.DeepFM import FM, DeepFM
 from pytorchrec_amd.model.DIN import DIN
@@ -24,6 +25,7 @@ _model_classes: Dict[str, Type[IModel]] = {
     "fm": FM,
     "deepfm": DeepFM,
     "dcnv2": DCNv2,
+    "dcnmix": DCNMix,
     "din": DIN,
     "dien": DIEN,
     "dlrm": DLRM,
