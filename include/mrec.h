@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MREC_ABI_VERSION 42
+#define MREC_ABI_VERSION 43
 #define MREC_MAX_TABLES 64      /* tables per table bank / per call */
 #define MREC_BWD_MAX_BATCH 8192  /* lookups per table per plan/apply call */
 #define MREC_BWD_HASH_MAX_BATCH 4096  /* batches up to this use the hash plan */
@@ -2308,6 +2308,86 @@ int64_t mrec_cross_mix_bwd_workspace_size(int64_t batch, int32_t d, int32_t K, i
                                           int32_t layers);
 mrec_status mrec_cross_mix_fwd(const mrec_cross_mix_args *args, mrec_stream stream);
 mrec_status mrec_cross_mix_bwd(const mrec_cross_mix_args *args, mrec_stream stream);
+
+/* ------------------------------------------------------------------------- */
+/* HSTU encoder, fused per sample, layer-major per workgroup (ABI 43; csrc/hstu.hip) */
+/* ------------------------------------------------------------------------- */
+/*
+ * The HSTU encoder (Zhai et al., ICML 2024: causal multi-head pointwise SiLU attention,
+ * a learned relative-position bias, a gating branch; every layer its own weights) in one
+ * launch each way.  Per sample b, with valid_j = his[b, j] > 0 or j == 0:
+ *   X      = bf16(rows[b L + j] + pos[(his_len[b] - j)]) at valid j, a zero row elsewhere
+ *   per layer l:
+ *     N = bf16(LayerNorm(X; norm1_w[l], norm1_b[l])), [U|V|Q|K] = bf16(SiLU(N w[l]^T + b[l]))
+ *     per head h of width D / H:  S = Q_h K_h^T + rab[l, h, i - j],
+ *       A = bf16(SiLU(S) att_scale) for j <= i and valid_j, exactly 0 elsewhere, C_h = bf16(A V_h)
+ *     G = bf16(LayerNorm(C; norm2_w[l], norm2_b[l]) U)
+ *     X <- bf16(X + G wo[l]^T + bo[l]) at valid rows, zero rows elsewhere
+ *   v[b]   = X[b, t_b], t_b the largest valid j                               (fp32)
+ * bf16 MFMA operands, fp32 accumulation / SiLU / LayerNorm statistics.  One description
+ * for both directions; the forward ignores the backward's fields.
+ *   rows, his, his_len, pos, d_oob_flag: as mrec_sasrec_args;
+ *   norm1_w, norm1_b, norm2_w, norm2_b, bo [num_layers, D], w [num_layers, 4 D, D],
+ *           b [num_layers, 4 D], wo [num_layers, D, D], rab [num_layers, H, rab_cols]
+ *           (rab_cols >= L): fp32 masters, contiguous, converted to bf16 in the kernel;
+ *   hs      [num_layers, batch, L, D] bf16, contiguous: the layer outputs, written by
+ *           the forward and read by the backward, which recomputes everything else;
+ *   v       [batch, D] fp32 (forward);
+ *   dv      [batch, D] fp32; carry [batch, L, D] fp32 scratch, a sample's dX between
+ *           layers (may be NULL with one layer); d_rows (row stride ld_drows) the rows'
+ *           bf16 gradient, bitwise zero at invalid positions; part
+ *           [parts][mrec_hstu_param_count] fp32 per-workgroup partials of every dense
+ *           gradient, flat and kind-major so that it splits into the stacked parameters:
+ *           [dw | dwo | db | dbo | dnorm1_w | dnorm1_b | dnorm2_w | dnorm2_b | drab], each
+ *           [num_layers, ...], then dpos (parts = mrec_hstu_parts(batch)).
+ * mrec_sasrec_wgrad sums the partials in workgroup order (bit-reproducible; no atomics
+ * anywhere).  Compiled shapes (mrec_hstu_supported): D in {16, 32, 64}, D / H in
+ * {16, 32, 64}, 1 <= L <= 64, 1 <= num_layers <= 4.  Stream-ordered, no allocation;
+ * anything else is MREC_EINVAL.
+ */
+typedef struct {
+  const void *rows;
+  int64_t ld_rows;
+  const int32_t *his;
+  int64_t ld_his;
+  const int32_t *his_len;
+  const float *pos;
+  int64_t ld_pos;
+  int32_t pos_rows;
+  const float *norm1_w;
+  const float *norm1_b;
+  const float *w;
+  const float *b;
+  const float *rab;
+  int32_t rab_cols;
+  const float *norm2_w;
+  const float *norm2_b;
+  const float *wo;
+  const float *bo;
+  float eps;
+  float att_scale;
+  int32_t num_layers;
+  int32_t H;
+  int64_t batch;
+  int32_t L;
+  int32_t D;
+  void *hs;
+  float *v;
+  int32_t *d_oob_flag;
+  const float *dv;
+  float *carry;
+  void *d_rows;
+  int64_t ld_drows;
+  float *part;
+  int64_t parts;
+} mrec_hstu_args;
+
+int32_t mrec_hstu_supported(int32_t D, int32_t H, int32_t L, int32_t num_layers);
+int64_t mrec_hstu_parts(int64_t batch);
+int64_t mrec_hstu_param_count(int32_t D, int32_t H, int32_t num_layers, int32_t rab_cols,
+                              int32_t pos_rows);
+mrec_status mrec_hstu_fwd(const mrec_hstu_args *args, mrec_stream stream);
+mrec_status mrec_hstu_bwd(const mrec_hstu_args *args, mrec_stream stream);
 
 #ifdef __cplusplus
 }

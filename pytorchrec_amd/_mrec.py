@@ -20,7 +20,7 @@ import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("MREC_LIB_PATH") or os.path.join(LIB_DIR, "libmrec.so")
 
-ABI_VERSION = 42
+ABI_VERSION = 43
 MAX_TABLES = 64
 BWD_MAX_BATCH = 8192
 BWD_HASH_MAX_BATCH = 4096  # batches up to this use the hash plan (fusable into a GEMM launch)
@@ -229,6 +229,26 @@ class SasrecArgs(ctypes.Structure):
                 ("batch", ctypes.c_int64), ("L", ctypes.c_int32), ("D", ctypes.c_int32),
                 ("hs", ctypes.c_void_p), ("v", ctypes.c_void_p), ("d_oob_flag", ctypes.c_void_p),
                 ("dv", ctypes.c_void_p), ("d_rows", ctypes.c_void_p), ("ld_drows", ctypes.c_int64),
+                ("part", ctypes.c_void_p), ("parts", ctypes.c_int64)]
+
+
+class HstuArgs(ctypes.Structure):
+    """mrec_hstu_args (include/mrec.h, ABI 43): one description for both directions."""
+    _fields_ = [("rows", ctypes.c_void_p), ("ld_rows", ctypes.c_int64),
+                ("his", ctypes.c_void_p), ("ld_his", ctypes.c_int64),
+                ("his_len", ctypes.c_void_p),
+                ("pos", ctypes.c_void_p), ("ld_pos", ctypes.c_int64), ("pos_rows", ctypes.c_int32),
+                ("norm1_w", ctypes.c_void_p), ("norm1_b", ctypes.c_void_p),
+                ("w", ctypes.c_void_p), ("b", ctypes.c_void_p),
+                ("rab", ctypes.c_void_p), ("rab_cols", ctypes.c_int32),
+                ("norm2_w", ctypes.c_void_p), ("norm2_b", ctypes.c_void_p),
+                ("wo", ctypes.c_void_p), ("bo", ctypes.c_void_p),
+                ("eps", ctypes.c_float), ("att_scale", ctypes.c_float),
+                ("num_layers", ctypes.c_int32), ("H", ctypes.c_int32),
+                ("batch", ctypes.c_int64), ("L", ctypes.c_int32), ("D", ctypes.c_int32),
+                ("hs", ctypes.c_void_p), ("v", ctypes.c_void_p), ("d_oob_flag", ctypes.c_void_p),
+                ("dv", ctypes.c_void_p), ("carry", ctypes.c_void_p),
+                ("d_rows", ctypes.c_void_p), ("ld_drows", ctypes.c_int64),
                 ("part", ctypes.c_void_p), ("parts", ctypes.c_int64)]
 
 
@@ -576,6 +596,11 @@ SIGNATURES = {
     "mrec_sasrec_fwd": (ctypes.c_int, [ctypes.POINTER(SasrecArgs), _vp]),
     "mrec_sasrec_bwd": (ctypes.c_int, [ctypes.POINTER(SasrecArgs), _vp]),
     "mrec_sasrec_wgrad": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp]),
+    "mrec_hstu_supported": (ctypes.c_int32, [_i32, _i32, _i32, _i32]),
+    "mrec_hstu_parts": (ctypes.c_int64, [_i64]),
+    "mrec_hstu_param_count": (ctypes.c_int64, [_i32, _i32, _i32, _i32, _i32]),
+    "mrec_hstu_fwd": (ctypes.c_int, [ctypes.POINTER(HstuArgs), _vp]),
+    "mrec_hstu_bwd": (ctypes.c_int, [ctypes.POINTER(HstuArgs), _vp]),
     "mrec_gru_supported": (ctypes.c_int32, [_i32, _i32, _i32]),
     "mrec_gru_tile": (ctypes.c_int32, []),
     "mrec_gru_parts": (ctypes.c_int64, [_i64]),

@@ -9,7 +9,8 @@ for a tensor on a GPU — those go through libmrec or raise.  ``neg_sample`` is 
 sampler of ``sampling.NegativeSampler``: the counter hash of ``mrec_neg_sample`` in
 numpy.  ``sasrec_encode`` is the SASRec encoder in torch ops: the CPU path, and on a GPU
 the layered path for the shapes and modes the fused kernels do not cover
-(``dense.sasrec_encode`` decides); ``gru_encode`` is the same for the GRU4Rec recurrence
+(``dense.sasrec_encode`` decides); ``hstu_encode`` is the same for the HSTU encoder
+(``dense.hstu_encode`` decides) and ``gru_encode`` for the GRU4Rec recurrence
 (``dense.gru_encode`` decides).  ``topk`` is ``mrec_topk``, the full-catalogue retrieval, in
 torch ops, chunked over the items (``retrieval.topk`` decides).  ``shared_negative_loss`` is
 ``mrec_shneg_loss_fwd`` / ``_bwd``, the list-wise losses over a shared pool of negatives, in
@@ -195,6 +196,60 @@ def sasrec_encode(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor, 
         x = r(torch.nn.functional.layer_norm(x + g, (D,), gamma.float(), beta.float(), eps))
     v = (x * valid.unsqueeze(-1).float()).sum(1)
     return v / his_len.unsqueeze(-1).float()
+
+
+def hstu_encode(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor, pos_w, norm1_w,
+                norm1_b, w, b, rab, norm2_w, norm2_b, wo, bo, eps: float, num_heads: int,
+                att_scale: float, dropout: float = 0.0, training: bool = False,
+                rnd=None) -> torch.Tensor:
+    """The HSTU encoder (Zhai et al., ICML 2024) in fp32 torch ops; autograd is its backward.
+
+    rows [B, L, D] item rows of the padded history, his [B, L] ids, his_len [B]; the
+    parameters stacked per kind, [layers, ...] -> v [B, D] = X[b, t_b], t_b the largest
+    valid position, after per layer (own weights)
+        N = LayerNorm(X), [U|V|Q|K] = SiLU(N W^T + b),
+        per head: A = SiLU(Q_h K_h^T + rab[h, i - j]) att_scale for j <= i and valid_j,
+                  exactly 0 elsewhere, C_h = A V_h,
+        X <- X + dropout(LayerNorm(concat C_h) U Wo^T + bo) at valid rows (invalid rows
+        stay zero rows).
+    Left out: HSTU's time-bucket bias (the data carries no timestamps) and a final output
+    normalisation.
+
+    ``rnd`` rounds X, the weight matrices, every matmul operand and each layer's output
+    (identity here; ``bf16_round`` on a GPU, where this is the layered path whose
+    rounding points are the fused kernel's).  A position id outside the table, or a
+    history longer than ``rab`` has columns, is IndexError."""
+    r = rnd if rnd is not None else (lambda t: t)
+    silu = torch.nn.functional.silu
+    B, L, D = rows.shape
+    H, layers = int(num_heads), w.shape[0]
+    dh = D // H
+    valid, pos = sasrec_positions(his, his_len)
+    if pos.numel() and (int(pos.min()) < 0 or int(pos.max()) >= pos_w.shape[0]):
+        raise IndexError("index out of range in self")
+    if L > rab.shape[-1]:
+        raise IndexError("index out of range in self")
+    vf = valid.unsqueeze(-1).float()
+    x = r(rows.float() + pos_w.float().index_select(0, pos.reshape(-1)).reshape(B, L, D)) * vf
+    j = torch.arange(L, device=rows.device)
+    delta = j[:, None] - j[None, :]
+    mask = ((delta >= 0)[None] & valid[:, None, :]).unsqueeze(1)  # [B, 1, L, L]
+    delta = delta.clamp(min=0)
+    zero = torch.zeros((), dtype=torch.float32, device=rows.device)
+    for l in range(layers):
+        n = r(torch.nn.functional.layer_norm(x, (D,), norm1_w[l].float(), norm1_b[l].float(), eps))
+        p = r(silu(n @ r(w[l].float()).t() + b[l].float()))
+        u, v, q, k = (t.reshape(B, L, H, dh).transpose(1, 2) for t in p.split(D, dim=-1))
+        s = q @ k.transpose(-1, -2) + rab[l].float()[:, delta]
+        a = torch.where(mask, r(silu(s) * att_scale), zero)
+        c = r(a @ v).transpose(1, 2).reshape(B, L, D)
+        c = torch.nn.functional.layer_norm(c, (D,), norm2_w[l].float(), norm2_b[l].float(), eps)
+        g = r(c * u.transpose(1, 2).reshape(B, L, D)) @ r(wo[l].float()).t() + bo[l].float()
+        if training and dropout > 0:
+            g = torch.nn.functional.dropout(g, p=dropout, training=True)
+        x = r(x + g) * vf
+    t = (valid.long() * j).max(dim=1).values
+    return x[torch.arange(B, device=rows.device), t]
 
 
 def gru_encode(rows: torch.Tensor, his_len: torch.Tensor, w_ih, w_hh, b_ih, b_hh,

@@ -1083,6 +1083,112 @@ def sasrec_encode(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor,
                                   rnd=cpu_path.bf16_round if rows.is_cuda else None)
 
 
+# the fused HSTU encoder (mrec_hstu_*, hstu.hip) is the default for the compiled shapes;
+# False selects the layered path (the parity tests set it)
+HSTU_FUSED = True
+
+
+def hstu_supported(D: int, H: int, L: int, num_layers: int = 1, dropout: float = 0.0,
+                   training: bool = False) -> bool:
+    """True when the fused encoder covers this block: D in {16, 32, 64}, heads of width 16,
+    32 or 64, L <= 64, 1 to 4 layers and no active dropout.  Decided from the shape alone;
+    never an error."""
+    if H < 1 or (training and dropout > 0):
+        return False
+    return bool(_mrec.lib().mrec_hstu_supported(int(D), int(H), int(L), int(num_layers)))
+
+
+def _hstu_params(model):
+    """The stacked parameters in the order of the kernel's partial (the position table last)."""
+    return (model.uvqk_weight, model.out_weight, model.uvqk_bias, model.out_bias,
+            model.norm1_weight, model.norm1_bias, model.norm2_weight, model.norm2_bias, model.rab,
+            model.p_embeddings.weight)
+
+
+class _HstuFn(torch.autograd.Function):
+    """The whole HSTU encoder over the gathered history rows [B, L, D]: one forward launch
+    (every layer -> v [B, D], the layer outputs saved), one backward launch (the rows' bf16
+    gradient + per-workgroup partials of the ten dense gradients) and the partials'
+    fixed-order sum."""
+
+    @staticmethod
+    def forward(ctx, rows, his, his_len, check: bool, eps: float, H: int, att_scale: float, w, wo,
+                b, bo, g1, be1, g2, be2, rab, pos):
+        B, L, D = rows.shape
+        dev = rows.device
+        layers = w.shape[0]
+        rows2 = _bf16_rows(rows.reshape(B * L, D))
+        his = his.to(torch.int32)
+        if his.stride(1) != 1:
+            his = his.contiguous()
+        his_len = his_len.reshape(-1).to(torch.int32).contiguous()
+        ws = [_f32c(t) for t in (w, wo, b, bo, g1, be1, g2, be2, rab)] + [_weight_f32(pos)]
+        hs = torch.empty(layers, B, L, D, dtype=_BF16, device=dev)
+        v = torch.empty(B, D, dtype=torch.float32, device=dev)
+        flag = torch.zeros(1, dtype=torch.int32, device=dev) if check else None
+        a = _mrec.HstuArgs(
+            rows2.data_ptr(), rows2.stride(0), his.data_ptr(), his.stride(0), his_len.data_ptr(),
+            ws[9].data_ptr(), ws[9].stride(0), ws[9].shape[0], ws[4].data_ptr(), ws[5].data_ptr(),
+            ws[0].data_ptr(), ws[2].data_ptr(), ws[8].data_ptr(), ws[8].shape[-1],
+            ws[6].data_ptr(), ws[7].data_ptr(), ws[1].data_ptr(), ws[3].data_ptr(), float(eps),
+            float(att_scale), int(layers), int(H), B, L, D, hs.data_ptr(), v.data_ptr(),
+            _mrec.ptr(flag), None, None, None, 0, None, 0)
+        if B:
+            _mrec.call("mrec_hstu_fwd", ctypes.byref(a), _mrec.stream_handle())
+        if flag is not None and int(flag.item()) != 0:
+            raise IndexError("index out of range in self")
+        a.d_oob_flag = None
+        ctx.args, ctx.keep = a, (rows2, his, his_len, ws, hs)
+        ctx.params = (w, wo, b, bo, g1, be1, g2, be2, rab, pos)
+        return v
+
+    @staticmethod
+    def backward(ctx, dv):
+        a, (rows2, his, his_len, ws, hs) = ctx.args, ctx.keep
+        params = ctx.params
+        B, L, D, layers, H = int(a.batch), int(a.L), int(a.D), int(a.num_layers), int(a.H)
+        dev = rows2.device
+        dv = dv.detach().float().contiguous()
+        d_rows = torch.empty(B * L, D, dtype=_BF16, device=dev)
+        # a sample's dX between layers (fp32; the kernel writes each row before it reads it)
+        carry = torch.empty(B * L, D, dtype=torch.float32, device=dev) if layers > 1 else None
+        a.dv, a.carry = dv.data_ptr(), _mrec.ptr(carry)
+        a.d_rows, a.ld_drows = d_rows.data_ptr(), d_rows.stride(0)
+        lib = _mrec.lib()
+        # the kernel's partial, kind-major: the stacked parameters in ``params`` order
+        sizes = [t.numel() for t in ws]
+        P = int(lib.mrec_hstu_param_count(D, H, layers, ws[8].shape[-1], ws[9].shape[0]))
+        assert sum(sizes) == P, (sizes, P)
+        grads = _sum_partials("mrec_hstu_bwd", a, B, int(lib.mrec_hstu_parts(B)), P, sizes, params,
+                              dev)
+        ctx.args = ctx.keep = None
+        return (d_rows.reshape(B, L, D), None, None, None, None, None, None) + grads
+
+
+def hstu_encode(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor,
+                model) -> torch.Tensor:
+    """v [B, D] (fp32) of the HSTU encoder over the gathered history rows [B, L, D] with
+    ``model``'s stacked per-layer parameters (model/HSTU.py).  On a GPU the fused kernels
+    when they cover the shape; else, on the CPU and when dropout is active, the layered
+    path: the same arithmetic as torch ops (``cpu_path.hstu_encode``), rounding to bf16 on
+    a GPU where the kernel does."""
+    from pytorchrec_amd import cpu_path
+    B, L, D = rows.shape
+    params = _hstu_params(model)
+    H, nl, eps = model.num_heads, model.num_layers, model.eps
+    att_scale = 1.0 / model.max_his_len
+    if (rows.is_cuda and HSTU_FUSED
+            and hstu_supported(D, H, L, nl, model.dropout, model.training)
+            and L <= model.rab.shape[-1]
+            and all(p.dtype == torch.float32 for p in params)):
+        check = bool(getattr(model.i_embeddings, "check_ids", True))
+        return _HstuFn.apply(rows, his, his_len, check, eps, H, att_scale, *params)
+    w, wo, b, bo, g1, be1, g2, be2, rab, pos = params
+    return cpu_path.hstu_encode(rows, his, his_len, pos, g1, be1, w, b, rab, g2, be2, wo, bo, eps,
+                                H, att_scale, dropout=model.dropout, training=model.training,
+                                rnd=cpu_path.bf16_round if rows.is_cuda else None)
+
+
 # the fused GRU4Rec encoder (mrec_gru_*, gru.hip) is the default for the compiled shapes;
 # False selects the layered path (the parity tests set it)
 GRU_FUSED = True

@@ -175,6 +175,11 @@ class SASRec(IModel):
         pad[:, 0] += his[:, 0] == 0  # position 0 is forced valid: the PAD row itself
         return torch.where(his > 0, his, pad).reshape(-1), True
 
+    def _encode(self, rows: Tensor, his: Tensor, his_len: Tensor) -> Tensor:
+        """v [B, D] of the gathered history rows [B, L, D] (a subclass with another encoder
+        over the same item bank, model/HSTU.py, replaces this)."""
+        return dense_ops.sasrec_encode(rows, his, his_len, self)
+
     def _encode_history(self, data: Dict[str, Tensor]) -> Tensor:
         """v [B, D] from a history-only lookup (``recommend``: no candidates to gather)."""
         his = self.his_column.get_feature_ids(data)
@@ -186,7 +191,7 @@ class SASRec(IModel):
         act_dtype = torch.bfloat16 if bank.weight.is_cuda else torch.float32
         hist_ids, padded = self._history_lookup_ids(his)
         rows = gather(bank, [hist_ids], out_dtype=act_dtype, pad_negative=padded)
-        return dense_ops.sasrec_encode(rows.reshape(B, L, self.emb_size), his, his_len, self)
+        return self._encode(rows.reshape(B, L, self.emb_size), his, his_len)
 
     def _retrieval_query(self, data: Dict[str, Tensor]):
         """``recommend``: the score is v . i, the query the encoder's output."""
@@ -216,7 +221,7 @@ class SASRec(IModel):
         B, L = his.shape
         cand = pos_ids if neg_ids is None else torch.cat([pos_ids, neg_ids.to(pos_ids.dtype)])
         rows = self._lookup_rows(his, cand)
-        v = dense_ops.sasrec_encode(rows[:B * L].reshape(B, L, self.emb_size), his, his_len, self)
+        v = self._encode(rows[:B * L].reshape(B, L, self.emb_size), his, his_len)
         pos_rows = rows[B * L:B * L + B]
         neg_rows = rows[B * L + B:] if neg_ids is not None else pos_rows
         return v.float(), pos_rows, neg_rows, pos_ids
@@ -233,7 +238,7 @@ class SASRec(IModel):
         B, N = i_ids.shape
         L, D = his.shape[1], self.emb_size
         rows = self._lookup_rows(his, i_ids.reshape(-1))
-        v = dense_ops.sasrec_encode(rows[:B * L].reshape(B, L, D), his, his_len, self)
+        v = self._encode(rows[:B * L].reshape(B, L, D), his, his_len)
         prediction = (v.unsqueeze(1) * rows[B * L:].reshape(B, N, D).float()).sum(-1)
         target = None
         if self.label_column is not None and self.label_column.feature_name in data:

@@ -8,6 +8,7 @@ from pytorchrec_amd.model.DIN import DIN
 from pytorchrec_amd.model.DLRM import DLRM
 from pytorchrec_amd.model.FunkSVD import FunkSVD
 from pytorchrec_amd.model.GRU4Rec import GRU4Rec
+from pytorchrec_amd.model.HSTU import HSTU
 from pytorchrec_amd.model.DIEN import DIEN
 from pytorchrec_amd.model.IModel import IModel
 from pytorchrec_amd.model.NCF import NCF
@@ -21,6 +22,7 @@ _model_classes: Dict[str, Type[IModel]] = {
     "svdpp": SVDPP,
     "sasrec": SASRec,
     "gru4rec": GRU4Rec,
+    "hstu": HSTU,
     "ncf": NCF,
     "fm": FM,
     "deepfm": DeepFM,
