@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MREC_ABI_VERSION 43
+#define MREC_ABI_VERSION 44
 #define MREC_MAX_TABLES 64      /* tables per table bank / per call */
 #define MREC_BWD_MAX_BATCH 8192  /* lookups per table per plan/apply call */
 #define MREC_BWD_HASH_MAX_BATCH 4096  /* batches up to this use the hash plan */
@@ -2388,6 +2388,64 @@ int64_t mrec_hstu_param_count(int32_t D, int32_t H, int32_t num_layers, int32_t 
                               int32_t pos_rows);
 mrec_status mrec_hstu_fwd(const mrec_hstu_args *args, mrec_stream stream);
 mrec_status mrec_hstu_bwd(const mrec_hstu_args *args, mrec_stream stream);
+
+/* ------------------------------------------------------------------------- */
+/* Normalised graph propagation, one layer per launch (ABI 44; csrc/graph_prop.hip) */
+/* ------------------------------------------------------------------------- */
+/*
+ * One LightGCN layer (He et al., SIGIR 2020) over a symmetric graph in CSR form, for
+ * every row r of the node table:
+ *   y[r] = dinv[r] * sum over c in col[row_ptr[r] .. row_ptr[r + 1]) of dinv[c] * src[c]
+ * with fp32 accumulation, and in the same pass
+ *   next[r]    = y[r]                     (fp32 or bf16, row stride dim; skipped when NULL)
+ *   acc_out[r] = acc_in[r] + y[r]         (fp32; divided by `divide` when it is not 0)
+ * so that K launches leave 1/(K+1) sum_k A^k x in the last launch's acc_out: the first
+ * launch takes acc_in = src = x, the middle ones acc_in = acc_out = the running sum, the
+ * last one next = NULL, divide = K + 1 and acc_out = the output.  With zero_pad the
+ * columns [dim, ld_acc_out) of every acc_out row are written as zero (an output laid out
+ * like a table bank).  acc_in may equal acc_out; src and next must not overlap.
+ *
+ * The work list is built once per graph (pytorchrec_amd/graph.py): work[w] = {row, len,
+ * slot, 0} and work_beg[w], one wave per entry, covering every row once: a row of up to
+ * MREC_GRAPH_LONG_ROW neighbours is one entry with slot = -1 (len 0: an isolated row);
+ * a longer row is cut into entries of at most MREC_GRAPH_LONG_ROW consecutive neighbours
+ * whose fp32 partial sums go to partial[slot * dim], and long_row[i] / long_ptr[i ..
+ * i + 1] name the row and its slots for the second pass, which adds them in slot order.
+ * No atomics: the bits of the result depend on the graph alone, not on the grid or the
+ * run.  Column ids must lie in [0, n_rows); the builder guarantees it, nothing here
+ * checks it.  dim in {8, 16, 32, 64}; src fp32 or bf16 with 16-byte aligned rows.
+ * n_rows == 0 launches nothing.  Stream-ordered, no allocation.
+ */
+#define MREC_GRAPH_LONG_ROW 256
+
+typedef struct {
+  int64_t n_rows;
+  int32_t dim;
+  const int32_t *col;   /* [edges] neighbour ids, ascending within a row */
+  const float *dinv;    /* [n_rows] deg^-1/2, 0 for an isolated row */
+  int64_t n_work;
+  const int32_t *work;  /* [n_work][4] = {row, len, slot or -1, 0} */
+  const int64_t *work_beg; /* [n_work] first edge of the entry */
+  int64_t n_long;
+  const int32_t *long_row; /* [n_long] */
+  const int32_t *long_ptr; /* [n_long + 1] slots of long row i */
+  float *partial;          /* [slots][dim] fp32 (may be NULL when n_long == 0) */
+  const void *src;         /* the layer that is gathered */
+  mrec_dtype src_dtype;
+  int64_t ld_src;          /* elements */
+  void *next;              /* [n_rows][dim] of next_dtype, or NULL */
+  mrec_dtype next_dtype;
+  const float *acc_in;
+  int64_t ld_acc_in;
+  float *acc_out;
+  int64_t ld_acc_out;
+  float divide;            /* 0: store the sum; else store sum / divide */
+  int32_t zero_pad;
+} mrec_graph_prop_args;
+
+int32_t mrec_graph_prop_supported(int32_t dim, mrec_dtype src_dtype, mrec_dtype next_dtype);
+int32_t mrec_graph_long_row(void);
+mrec_status mrec_graph_prop(const mrec_graph_prop_args *args, mrec_stream stream);
 
 #ifdef __cplusplus
 }

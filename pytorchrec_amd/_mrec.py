@@ -20,7 +20,7 @@ import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("MREC_LIB_PATH") or os.path.join(LIB_DIR, "libmrec.so")
 
-ABI_VERSION = 43
+ABI_VERSION = 44
 MAX_TABLES = 64
 BWD_MAX_BATCH = 8192
 BWD_HASH_MAX_BATCH = 4096  # batches up to this use the hash plan (fusable into a GEMM launch)
@@ -250,6 +250,21 @@ class HstuArgs(ctypes.Structure):
                 ("dv", ctypes.c_void_p), ("carry", ctypes.c_void_p),
                 ("d_rows", ctypes.c_void_p), ("ld_drows", ctypes.c_int64),
                 ("part", ctypes.c_void_p), ("parts", ctypes.c_int64)]
+
+
+class GraphPropArgs(ctypes.Structure):
+    """mrec_graph_prop_args (include/mrec.h, ABI 44): one propagation layer."""
+    _fields_ = [("n_rows", ctypes.c_int64), ("dim", ctypes.c_int32),
+                ("col", ctypes.c_void_p), ("dinv", ctypes.c_void_p),
+                ("n_work", ctypes.c_int64), ("work", ctypes.c_void_p),
+                ("work_beg", ctypes.c_void_p),
+                ("n_long", ctypes.c_int64), ("long_row", ctypes.c_void_p),
+                ("long_ptr", ctypes.c_void_p), ("partial", ctypes.c_void_p),
+                ("src", ctypes.c_void_p), ("src_dtype", ctypes.c_int), ("ld_src", ctypes.c_int64),
+                ("next", ctypes.c_void_p), ("next_dtype", ctypes.c_int),
+                ("acc_in", ctypes.c_void_p), ("ld_acc_in", ctypes.c_int64),
+                ("acc_out", ctypes.c_void_p), ("ld_acc_out", ctypes.c_int64),
+                ("divide", ctypes.c_float), ("zero_pad", ctypes.c_int32)]
 
 
 class GruArgs(ctypes.Structure):
@@ -601,6 +616,9 @@ SIGNATURES = {
     "mrec_hstu_param_count": (ctypes.c_int64, [_i32, _i32, _i32, _i32, _i32]),
     "mrec_hstu_fwd": (ctypes.c_int, [ctypes.POINTER(HstuArgs), _vp]),
     "mrec_hstu_bwd": (ctypes.c_int, [ctypes.POINTER(HstuArgs), _vp]),
+    "mrec_graph_prop_supported": (ctypes.c_int32, [_i32, ctypes.c_int, ctypes.c_int]),
+    "mrec_graph_long_row": (ctypes.c_int32, []),
+    "mrec_graph_prop": (ctypes.c_int, [ctypes.POINTER(GraphPropArgs), _vp]),
     "mrec_gru_supported": (ctypes.c_int32, [_i32, _i32, _i32]),
     "mrec_gru_tile": (ctypes.c_int32, []),
     "mrec_gru_parts": (ctypes.c_int64, [_i64]),

@@ -920,3 +920,27 @@ def cross_mix(x0, layers, round_bf16: bool = False, chunk: int = 1024):
         flat += [w for w in l if w is not None]
     y = _CrossMixFn.apply(x0, (K, int(chunk), bf16_round_any if round_bf16 else None), *flat)
     return y.to(torch.bfloat16) if round_bf16 else y
+
+
+def graph_propagate(graph, x: torch.Tensor, n_layers: int, layer_dtype=None) -> torch.Tensor:
+    """The LightGCN propagation, and the definition ``mrec_graph_prop`` is held to
+    (``graph.propagate`` decides):  with A^ = D^-1/2 A D^-1/2 over ``graph``,
+
+        E_out = (sum_{k=0..K} A^^k x) / (K + 1),   y_{k+1}[r] = dinv[r] sum_c dinv[c] y_k[c]
+
+    on ``x [N, D]`` in the dtype of ``x`` (fp64 included), differentiable.  An isolated node
+    has dinv 0: its layers are zero and its output x / (K + 1).  ``layer_dtype`` bfloat16
+    rounds each layer where it is stored as the next layer's source; the running sum takes
+    the unrounded layer."""
+    if layer_dtype not in (None, torch.float32, torch.bfloat16):
+        raise ValueError(f"layer_dtype must be None, float32 or bfloat16, got {layer_dtype}")
+    if x.dim() != 2 or x.shape[0] != graph.n_nodes:
+        raise ValueError(f"x must be [{graph.n_nodes}, D], got {tuple(x.shape)}")
+    rows, col = graph.edge_rows(), graph.col.long()
+    dinv = graph.dinv.to(x.dtype).unsqueeze(1)
+    total, y = x, x
+    for _ in range(int(n_layers)):
+        src = y.to(torch.bfloat16).to(x.dtype) if layer_dtype == torch.bfloat16 and y is not x else y
+        y = dinv * torch.zeros_like(x).index_add_(0, rows, (dinv * src).index_select(0, col))
+        total = total + y
+    return total / (int(n_layers) + 1)

@@ -114,11 +114,17 @@ class FunkSVD(IModel):
 
     candidate_lists = True
 
+    def _bank(self) -> EmbeddingBank:
+        """The two-table bank the scores are read from, asked for once per call (LightGCN
+        returns this step's propagated table here)."""
+        return self.embeddings
+
     def _retrieval_query(self, data: Dict[str, Tensor]):
         """``recommend``: the score is u . i, the query the user row."""
         u_ids = self.uid_column.get_feature_ids(data)
-        rows = gather(self.embeddings, [u_ids, torch.zeros_like(u_ids)], out_dtype=torch.float32)
-        return rows[:, :self.emb_size], self.embeddings, 1, False, None
+        bank = self._bank()
+        rows = gather(bank, [u_ids, torch.zeros_like(u_ids)], out_dtype=torch.float32)
+        return rows[:, :self.emb_size], bank, 1, False, None
 
     def _shared_negative_inputs(self, data: Dict[str, Tensor], neg_ids):
         """Users, positives and the pool in ONE gather of the two-table bank: the pool's
@@ -126,7 +132,7 @@ class FunkSVD(IModel):
         row is looked up, and updated, once.  q is the user row, as in ``_retrieval_query``."""
         u_ids = self.uid_column.get_feature_ids(data)
         pos_ids = self._shared_positive_ids(data)
-        bank, D = self.embeddings, self.emb_size
+        bank, D = self._bank(), self.emb_size
         B = u_ids.shape[0]
         padded = bank.weight.is_cuda
         i_ids = pos_ids.to(u_ids.dtype)
@@ -146,8 +152,9 @@ class FunkSVD(IModel):
     def forward(self, data: Dict[str, Tensor]):
         u_ids = self.uid_column.get_feature_ids(data)
         i_ids = self.iid_column.get_feature_ids(data)
+        bank = self._bank()
         if i_ids.dim() == 1:
-            prediction = interact(self.embeddings, [u_ids, i_ids], fm2=True, first_order=False)
+            prediction = interact(bank, [u_ids, i_ids], fm2=True, first_order=False)
             target = None
             if self.label_column is not None and self.label_column.feature_name in data:
                 target = data[self.label_column.feature_name].float()
@@ -156,7 +163,7 @@ class FunkSVD(IModel):
         # 2-field interaction row
         B, N = i_ids.shape
         uu = u_ids.reshape(B, 1).expand(B, N).reshape(-1).contiguous()
-        prediction = interact(self.embeddings, [uu, i_ids.reshape(-1).contiguous()], fm2=True,
+        prediction = interact(bank, [uu, i_ids.reshape(-1).contiguous()], fm2=True,
                               first_order=False).reshape(B, N)
         target = torch.zeros_like(prediction, dtype=torch.float32)
         target[:, 0] = 1

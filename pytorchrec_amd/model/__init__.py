@@ -14,4 +14,5 @@ from pytorchrec_amd.model.GRU4Rec import GRU4Rec
 from pytorchrec_amd.model.HSTU import HSTU
 from pytorchrec_amd.model.DIEN import DIEN
 from pytorchrec_amd.model.NCF import NCF
+from pytorchrec_amd.model.LightGCN import LightGCN
 from pytorchrec_amd.model.models import get_model_type, model_name_list
