@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MREC_ABI_VERSION 44
+#define MREC_ABI_VERSION 45
 #define MREC_MAX_TABLES 64      /* tables per table bank / per call */
 #define MREC_BWD_MAX_BATCH 8192  /* lookups per table per plan/apply call */
 #define MREC_BWD_HASH_MAX_BATCH 4096  /* batches up to this use the hash plan */
@@ -2446,6 +2446,69 @@ typedef struct {
 int32_t mrec_graph_prop_supported(int32_t dim, mrec_dtype src_dtype, mrec_dtype next_dtype);
 int32_t mrec_graph_long_row(void);
 mrec_status mrec_graph_prop(const mrec_graph_prop_args *args, mrec_stream stream);
+
+/* ------------------------------------------------------------------------- */
+/* MIND multi-interest routing, fused per sample, one wave each (ABI 45; csrc/mind.hip) */
+/* ------------------------------------------------------------------------- */
+/*
+ * Behaviour-to-interest dynamic routing (MIND, Li et al., CIKM 2019; ComiRec-DR, Cen et
+ * al., KDD 2020) of a history into K interest capsules, one launch each way.  Per sample b,
+ * with valid_j = his[b, j] > 0 or j == 0, and K' = K, or with dynamic_k
+ * K' = max(1, min(K, floor(log2(max(his_len[b], 1))))):
+ *   H^_j = bf16(X_j route_w^T), X_j = rows[b L + j] at valid j, a zero row elsewhere
+ *   b_kj = route_init[k, j]
+ *   for r = 1 .. iters:
+ *     w_kj = bf16(softmax over k < K' of b_kj) at valid j, exactly 0 elsewhere and at k >= K'
+ *     z_k  = sum_j w_kj H^_j;  u_k = z_k n2 / ((1 + n2) sqrt(n2 + 1e-9)), n2 = |z_k|^2
+ *     if r < iters:  b_kj += bf16(u_k) . H^_j
+ * bf16 MFMA operands, fp32 accumulation, softmax and squash.  One description for both
+ * directions; the forward ignores the backward's fields.
+ *   rows, his, his_len: as mrec_sasrec_args (bf16 rows, 16-byte aligned);
+ *   route_w [D, D] fp32 master (row stride ld_w, 16-byte aligned rows), converted to bf16
+ *           in the kernel; route_init [K, >= L] fp32 (row stride ld_init);
+ *   u       [batch, K, D] fp32: the last iteration's capsules, rows k >= K' exactly zero;
+ *   w       [batch, K, L] bf16 and z [batch, K, D] fp32, contiguous: the last iteration's
+ *           coupling (the values its product used) and pre-squash capsules, written by the
+ *           forward and read by the backward;
+ *   du      [batch, K, D] fp32; d_rows (row stride ld_drows) the rows' bf16 gradient,
+ *           bitwise zero at invalid positions; part [parts][D * D] fp32 per-workgroup
+ *           partials of d route_w (parts = mrec_mind_parts(batch)), to be summed in
+ *           workgroup order by mrec_sasrec_wgrad.
+ * The routing logits carry no gradient: the last w is a constant and du flows through the
+ * squash and z = w H^ only.  No atomics: two runs give equal bits.  Compiled shapes
+ * (mrec_mind_supported): D in {16, 32, 64}, 1 <= K <= 8, 1 <= L <= 64, 1 <= iters <= 4.
+ * Stream-ordered, no allocation; anything else is MREC_EINVAL.
+ */
+typedef struct {
+  const void *rows;
+  int64_t ld_rows;
+  const int32_t *his;
+  int64_t ld_his;
+  const int32_t *his_len;
+  const float *route_w;
+  int64_t ld_w;
+  const float *route_init;
+  int64_t ld_init;
+  int64_t batch;
+  int32_t L;
+  int32_t D;
+  int32_t K;
+  int32_t iters;
+  int32_t dynamic_k;
+  float *u;
+  void *w;
+  float *z;
+  const float *du;
+  void *d_rows;
+  int64_t ld_drows;
+  float *part;
+  int64_t parts;
+} mrec_mind_args;
+
+int32_t mrec_mind_supported(int32_t D, int32_t K, int32_t L, int32_t iters);
+int64_t mrec_mind_parts(int64_t batch);
+mrec_status mrec_mind_fwd(const mrec_mind_args *args, mrec_stream stream);
+mrec_status mrec_mind_bwd(const mrec_mind_args *args, mrec_stream stream);
 
 #ifdef __cplusplus
 }

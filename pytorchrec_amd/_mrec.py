@@ -20,7 +20,7 @@ import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("MREC_LIB_PATH") or os.path.join(LIB_DIR, "libmrec.so")
 
-ABI_VERSION = 44
+ABI_VERSION = 45
 MAX_TABLES = 64
 BWD_MAX_BATCH = 8192
 BWD_HASH_MAX_BATCH = 4096  # batches up to this use the hash plan (fusable into a GEMM launch)
@@ -265,6 +265,21 @@ class GraphPropArgs(ctypes.Structure):
                 ("acc_in", ctypes.c_void_p), ("ld_acc_in", ctypes.c_int64),
                 ("acc_out", ctypes.c_void_p), ("ld_acc_out", ctypes.c_int64),
                 ("divide", ctypes.c_float), ("zero_pad", ctypes.c_int32)]
+
+
+class MindArgs(ctypes.Structure):
+    """mrec_mind_args (include/mrec.h, ABI 45): one description for both directions."""
+    _fields_ = [("rows", ctypes.c_void_p), ("ld_rows", ctypes.c_int64),
+                ("his", ctypes.c_void_p), ("ld_his", ctypes.c_int64),
+                ("his_len", ctypes.c_void_p),
+                ("route_w", ctypes.c_void_p), ("ld_w", ctypes.c_int64),
+                ("route_init", ctypes.c_void_p), ("ld_init", ctypes.c_int64),
+                ("batch", ctypes.c_int64), ("L", ctypes.c_int32), ("D", ctypes.c_int32),
+                ("K", ctypes.c_int32), ("iters", ctypes.c_int32), ("dynamic_k", ctypes.c_int32),
+                ("u", ctypes.c_void_p), ("w", ctypes.c_void_p), ("z", ctypes.c_void_p),
+                ("du", ctypes.c_void_p),
+                ("d_rows", ctypes.c_void_p), ("ld_drows", ctypes.c_int64),
+                ("part", ctypes.c_void_p), ("parts", ctypes.c_int64)]
 
 
 class GruArgs(ctypes.Structure):
@@ -616,6 +631,10 @@ SIGNATURES = {
     "mrec_hstu_param_count": (ctypes.c_int64, [_i32, _i32, _i32, _i32, _i32]),
     "mrec_hstu_fwd": (ctypes.c_int, [ctypes.POINTER(HstuArgs), _vp]),
     "mrec_hstu_bwd": (ctypes.c_int, [ctypes.POINTER(HstuArgs), _vp]),
+    "mrec_mind_supported": (ctypes.c_int32, [_i32, _i32, _i32, _i32]),
+    "mrec_mind_parts": (ctypes.c_int64, [_i64]),
+    "mrec_mind_fwd": (ctypes.c_int, [ctypes.POINTER(MindArgs), _vp]),
+    "mrec_mind_bwd": (ctypes.c_int, [ctypes.POINTER(MindArgs), _vp]),
     "mrec_graph_prop_supported": (ctypes.c_int32, [_i32, ctypes.c_int, ctypes.c_int]),
     "mrec_graph_long_row": (ctypes.c_int32, []),
     "mrec_graph_prop": (ctypes.c_int, [ctypes.POINTER(GraphPropArgs), _vp]),

@@ -10,7 +10,8 @@ sampler of ``sampling.NegativeSampler``: the counter hash of ``mrec_neg_sample``
 numpy.  ``sasrec_encode`` is the SASRec encoder in torch ops: the CPU path, and on a GPU
 the layered path for the shapes and modes the fused kernels do not cover
 (``dense.sasrec_encode`` decides); ``hstu_encode`` is the same for the HSTU encoder
-(``dense.hstu_encode`` decides) and ``gru_encode`` for the GRU4Rec recurrence
+(``dense.hstu_encode`` decides), ``mind_route`` for MIND's capsule routing
+(``dense.mind_route`` decides) and ``gru_encode`` for the GRU4Rec recurrence
 (``dense.gru_encode`` decides).  ``topk`` is ``mrec_topk``, the full-catalogue retrieval, in
 torch ops, chunked over the items (``retrieval.topk`` decides).  ``shared_negative_loss`` is
 ``mrec_shneg_loss_fwd`` / ``_bwd``, the list-wise losses over a shared pool of negatives, in
@@ -250,6 +251,61 @@ def hstu_encode(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor, po
         x = r(x + g) * vf
     t = (valid.long() * j).max(dim=1).values
     return x[torch.arange(B, device=rows.device), t]
+
+
+def mind_active(his_len: torch.Tensor, K: int, dynamic_k: bool) -> torch.Tensor:
+    """Active interests per sample [B]: K, or MIND's adaptive count max(1, min(K,
+    floor(log2(max(his_len, 1))))) (frexp: the exponent is exact)."""
+    lens = his_len.reshape(-1)
+    if not dynamic_k:
+        return torch.full_like(lens, int(K), dtype=torch.int64)
+    return (torch.frexp(lens.clamp(min=1).float())[1].long() - 1).clamp(min=1, max=int(K))
+
+
+def mind_route(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor, route_weight,
+               route_init, iters: int, dynamic_k: bool = False, rnd=None) -> torch.Tensor:
+    """MIND's behaviour-to-interest dynamic routing (Li et al., CIKM 2019; ComiRec-DR, Cen
+    et al., KDD 2020) in fp32 torch ops; autograd is its backward.
+
+    rows [B, L, D] item rows of the padded history, his [B, L] ids, his_len [B],
+    route_weight S [D, D], route_init [K, >= L] -> U [B, K, D]:
+        H^_j = X_j S^T,  b_kj = route_init[k, j]
+        R times: w_kj = softmax over k < K'_b of b_kj at valid j, exactly 0 at invalid j and
+                 k >= K'_b;  z_k = sum_j w_kj H^_j;
+                 u_k = z_k n2 / ((1 + n2) sqrt(n2 + 1e-9)), n2 = |z_k|^2;
+                 b_kj += u_k . H^_j (not after the last)
+    U is the last u; its rows k >= K'_b (``mind_active``) are exactly zero.  The routing
+    logits carry no gradient (MIND 4.2; ComiRec-DR's code stops it the same way): every
+    w is detached, so dU flows through the squash and the last z = w H^ only.
+
+    ``rnd`` rounds X, S, H^ and the two routing operands w and u (identity here;
+    ``bf16_round`` on a GPU, where this is the layered path whose rounding points are the
+    fused kernel's).  A history longer than ``route_init`` has columns is IndexError."""
+    r = rnd if rnd is not None else (lambda t: t)
+    B, L, D = rows.shape
+    K = route_init.shape[0]
+    if L > route_init.shape[1]:
+        raise IndexError("index out of range in self")
+    valid, _ = sasrec_positions(his, his_len)
+    act = torch.arange(K, device=rows.device)[None, :] < mind_active(his_len, K, dynamic_k)[:, None]
+    mask = act[:, :, None] & valid[:, None, :]  # [B, K, L]
+    zero = torch.zeros((), dtype=torch.float32, device=rows.device)
+    # (where, not a product: an invalid row is a zero row whatever it holds, inf and NaN too)
+    x = torch.where(valid.unsqueeze(-1), r(rows.float()), zero)
+    h = r(x @ r(route_weight.float()).t())
+    hd = h.detach()
+    b = route_init[:, :L].float().unsqueeze(0).expand(B, K, L)
+    u = None
+    for it in range(int(iters)):
+        last = it == int(iters) - 1
+        w = torch.softmax(b.masked_fill(~act[:, :, None], float("-inf")), dim=1)
+        w = r(torch.where(mask, w, zero)).detach()
+        z = torch.bmm(w, h if last else hd)
+        n2 = (z * z).sum(-1, keepdim=True)
+        u = z * (n2 / ((1.0 + n2) * torch.sqrt(n2 + 1e-9)))
+        if not last:
+            b = b + torch.bmm(r(u.detach()), hd.transpose(1, 2))
+    return u
 
 
 def gru_encode(rows: torch.Tensor, his_len: torch.Tensor, w_ih, w_hh, b_ih, b_hh,

@@ -1189,6 +1189,78 @@ def hstu_encode(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor,
                                 rnd=cpu_path.bf16_round if rows.is_cuda else None)
 
 
+# the fused MIND routing (mrec_mind_*, mind.hip) is the default for the compiled shapes;
+# False selects the layered path (the parity tests set it)
+MIND_FUSED = True
+
+
+def mind_supported(D: int, K: int, L: int, iters: int) -> bool:
+    """True when the fused routing covers this shape: D in {16, 32, 64}, 1 to 8 interests,
+    L <= 64 and 1 to 4 iterations.  Decided from the shape alone; never an error."""
+    return bool(_mrec.lib().mrec_mind_supported(int(D), int(K), int(L), int(iters)))
+
+
+class _MindFn(torch.autograd.Function):
+    """MIND's dynamic routing over the gathered history rows [B, L, D]: one forward launch
+    (U [B, K, D]; the last coupling w and the pre-squash z saved), one backward launch (the
+    rows' bf16 gradient + per-workgroup partials of d route_weight) and the partials'
+    fixed-order sum."""
+
+    @staticmethod
+    def forward(ctx, rows, his, his_len, iters: int, dynamic_k: bool, route_init, route_weight):
+        B, L, D = rows.shape
+        K = route_init.shape[0]
+        dev = rows.device
+        rows2 = _bf16_rows(rows.reshape(B * L, D))
+        his = his.to(torch.int32)
+        if his.stride(1) != 1:
+            his = his.contiguous()
+        his_len = his_len.reshape(-1).to(torch.int32).contiguous()
+        s, init = _f32c(route_weight), _weight_f32(route_init)
+        u = torch.empty(B, K, D, dtype=torch.float32, device=dev)
+        w = torch.empty(B, K, L, dtype=_BF16, device=dev)
+        z = torch.empty(B, K, D, dtype=torch.float32, device=dev)
+        a = _mrec.MindArgs(
+            rows2.data_ptr(), rows2.stride(0), his.data_ptr(), his.stride(0), his_len.data_ptr(),
+            s.data_ptr(), s.stride(0), init.data_ptr(), init.stride(0), B, L, D, K, int(iters),
+            int(bool(dynamic_k)), u.data_ptr(), w.data_ptr(), z.data_ptr(), None, None, 0, None, 0)
+        if B:
+            _mrec.call("mrec_mind_fwd", ctypes.byref(a), _mrec.stream_handle())
+        ctx.args, ctx.keep, ctx.param = a, (rows2, his, his_len, s, init, w, z), route_weight
+        return u
+
+    @staticmethod
+    def backward(ctx, du):
+        a, keep, route_weight = ctx.args, ctx.keep, ctx.param
+        B, L, D = int(a.batch), int(a.L), int(a.D)
+        dev = keep[0].device
+        du = du.detach().float().contiguous()
+        d_rows = torch.empty(B * L, D, dtype=_BF16, device=dev)
+        a.du, a.d_rows, a.ld_drows = du.data_ptr(), d_rows.data_ptr(), d_rows.stride(0)
+        parts = int(_mrec.lib().mrec_mind_parts(B))
+        grads = _sum_partials("mrec_mind_bwd", a, B, parts, D * D, [D * D], (route_weight,), dev)
+        ctx.args = ctx.keep = None
+        return (d_rows.reshape(B, L, D), None, None, None, None, None) + grads
+
+
+def mind_route(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor,
+               model) -> torch.Tensor:
+    """U [B, K, D] (fp32), the interest capsules of MIND's dynamic routing over the gathered
+    history rows [B, L, D] with ``model``'s ``route_weight``, ``route_init``,
+    ``routing_iters`` and ``dynamic_k`` (model/MIND.py).  On a GPU the fused kernels when
+    they cover the shape; else, and on the CPU, the layered path: the same arithmetic as
+    torch ops (``cpu_path.mind_route``), rounding to bf16 on a GPU where the kernel does."""
+    from pytorchrec_amd import cpu_path
+    B, L, D = rows.shape
+    S, init = model.route_weight, model.route_init
+    K, iters = init.shape[0], int(model.routing_iters)
+    if (rows.is_cuda and MIND_FUSED and mind_supported(D, K, L, iters) and L <= init.shape[1]
+            and S.dtype == torch.float32 and tuple(S.shape) == (D, D)):
+        return _MindFn.apply(rows, his, his_len, iters, bool(model.dynamic_k), init, S)
+    return cpu_path.mind_route(rows, his, his_len, S, init, iters, bool(model.dynamic_k),
+                               rnd=cpu_path.bf16_round if rows.is_cuda else None)
+
+
 # the fused GRU4Rec encoder (mrec_gru_*, gru.hip) is the default for the compiled shapes;
 # False selects the layered path (the parity tests set it)
 GRU_FUSED = True

@@ -12,6 +12,7 @@ from pytorchrec_amd.model.SVDPP import SVDPP
 from pytorchrec_amd.model.SASRec import SASRec
 from pytorchrec_amd.model.GRU4Rec import GRU4Rec
 from pytorchrec_amd.model.HSTU import HSTU
+from pytorchrec_amd.model.MIND import MIND
 from pytorchrec_amd.model.DIEN import DIEN
 from pytorchrec_amd.model.NCF import NCF
 from pytorchrec_amd.model.LightGCN import LightGCN
