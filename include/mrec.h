@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MREC_ABI_VERSION 45
+#define MREC_ABI_VERSION 46
 #define MREC_MAX_TABLES 64      /* tables per table bank / per call */
 #define MREC_BWD_MAX_BATCH 8192  /* lookups per table per plan/apply call */
 #define MREC_BWD_HASH_MAX_BATCH 4096  /* batches up to this use the hash plan */
@@ -2509,6 +2509,93 @@ int32_t mrec_mind_supported(int32_t D, int32_t K, int32_t L, int32_t iters);
 int64_t mrec_mind_parts(int64_t batch);
 mrec_status mrec_mind_fwd(const mrec_mind_args *args, mrec_stream stream);
 mrec_status mrec_mind_bwd(const mrec_mind_args *args, mrec_stream stream);
+
+/* ------------------------------------------------------------------------- */
+/* SR-GNN session encoder, fused per sample, one launch each way (ABI 46; csrc/srgnn.hip) */
+/* ------------------------------------------------------------------------- */
+/*
+ * The session-graph gated GNN and attention readout of SR-GNN (Wu et al., AAAI 2019), one
+ * launch each way for the batch.  Per sample b, with valid_j = his[b, j] > 0 or j == 0, positions
+ * ascending in time and t_1 < ... < t_n the valid ones:
+ *   alias(t) = the first valid position with the id of t (the node's representative);
+ *   edge a -> b when alias(t_k) = a and alias(t_k+1) = b for some k (binary: a repeated
+ *   transition is one edge; an item following itself is a self-loop); indeg / outdeg count
+ *   distinct edges and a degree of 0 divides as 1;
+ *   H^0_a = rows[b L + a] at representatives (rows at duplicate and invalid positions are
+ *   never read; those tile rows are unused: no edge touches them);
+ *   steps times:
+ *     E_in = bf16(H w_ein^T + b_ein), E_out = bf16(H w_eout^T + b_eout)
+ *     M_in_b = bf16(1/indeg(b) sum_{a->b} E_in_a + b_iah), M_out_a = bf16(1/outdeg(a)
+ *              sum_{a->b} E_out_b + b_oah)
+ *     gi = [M_in | M_out] w_ih^T + b_ih, gh = H w_hh^T + b_hh   (gate order r, z, c)
+ *     r = sigmoid(gi_r + gh_r), z = sigmoid(gi_z + gh_z), c = tanh(gi_c + r gh_c)
+ *     H <- bf16(c + z (H - c))
+ *   h_last = H[alias(t_n)], alpha_k = q . sigmoid(w1 h_last + w2 H[alias(t_k)] + c1),
+ *   g = sum_k alpha_k H[alias(t_k)] (over positions: an item seen twice counts twice),
+ *   v = wt [g | h_last] + bt.
+ * bf16 MFMA operands (H, E, M and the matrices w_ein, w_eout, w_ih, w_hh, w1, w2, converted
+ * from their fp32 masters in the kernel); the adjacency is binary, exact in bf16, and 1/deg
+ * is applied in fp32 on the accumulators; fp32 accumulation, gates, readout sums, and the
+ * last product, which takes wt and g as fp32.
+ *   rows, his: as mrec_sasrec_args (bf16 rows, 16-byte aligned);
+ *   w_ein, w_eout, w1, w2 [D, D], w_ih [3 D, 2 D], w_hh [3 D, D], wt [D, 2 D]: contiguous
+ *   fp32, the six MFMA matrices 16-byte aligned; b_ih, b_hh [3 D]; the other vectors [D];
+ *   v [batch, D] fp32, contiguous;
+ *   hs [steps, batch, L, D] bf16, contiguous, 16-byte aligned: H after each step, written by
+ *   the forward when not NULL (NULL: a forward that nobody differentiates) and read by the
+ *   backward, which recomputes each step from its input (H^0 from the rows);
+ *   dv [batch, D] fp32; d_rows (row stride ld_drows) the rows' bf16 gradient: a node's whole
+ *   gradient on its representative position, bitwise zero at invalid and duplicate positions;
+ *   part [parts][mrec_srgnn_param_count(D) = 15 D D + 13 D] fp32 per-workgroup partials of the
+ *   dense gradients in the order w_ein, w_eout, w_ih, w_hh, w1, w2, wt, b_ein, b_eout, b_iah,
+ *   b_oah, b_ih, b_hh, c1, q, bt (parts = mrec_srgnn_parts(batch)), to be summed in workgroup
+ *   order by mrec_sasrec_wgrad.  The backward rounds dG, dM and dE to bf16 as MFMA operands
+ *   and accumulates everything in fp32.
+ * One description for both directions; the forward ignores the backward's fields.  No
+ * atomics, and a sample's v and d_rows depend on that sample alone: two runs, and two batch
+ * orders, give equal bits.  Compiled shapes (mrec_srgnn_supported): D in {16, 32, 64},
+ * 1 <= L <= 64, 1 <= steps <= 4; anything else is MREC_EINVAL before any device work.
+ * Stream-ordered, no allocation.
+ */
+typedef struct {
+  const void *rows;
+  int64_t ld_rows;
+  const int32_t *his;
+  int64_t ld_his;
+  const float *w_ein;
+  const float *w_eout;
+  const float *w_ih;
+  const float *w_hh;
+  const float *w1;
+  const float *w2;
+  const float *wt;
+  const float *b_ein;
+  const float *b_eout;
+  const float *b_iah;
+  const float *b_oah;
+  const float *b_ih;
+  const float *b_hh;
+  const float *c1;
+  const float *q;
+  const float *bt;
+  int64_t batch;
+  int32_t L;
+  int32_t D;
+  int32_t steps;
+  float *v;
+  void *hs;
+  const float *dv;
+  void *d_rows;
+  int64_t ld_drows;
+  float *part;
+  int64_t parts;
+} mrec_srgnn_args;
+
+int32_t mrec_srgnn_supported(int32_t D, int32_t L, int32_t steps);
+int64_t mrec_srgnn_parts(int64_t batch);
+int64_t mrec_srgnn_param_count(int32_t D);
+mrec_status mrec_srgnn_fwd(const mrec_srgnn_args *args, mrec_stream stream);
+mrec_status mrec_srgnn_bwd(const mrec_srgnn_args *args, mrec_stream stream);
 
 #ifdef __cplusplus
 }

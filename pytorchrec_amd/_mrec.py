@@ -20,7 +20,7 @@ import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("MREC_LIB_PATH") or os.path.join(LIB_DIR, "libmrec.so")
 
-ABI_VERSION = 45
+ABI_VERSION = 46
 MAX_TABLES = 64
 BWD_MAX_BATCH = 8192
 BWD_HASH_MAX_BATCH = 4096  # batches up to this use the hash plan (fusable into a GEMM launch)
@@ -280,6 +280,19 @@ class MindArgs(ctypes.Structure):
                 ("du", ctypes.c_void_p),
                 ("d_rows", ctypes.c_void_p), ("ld_drows", ctypes.c_int64),
                 ("part", ctypes.c_void_p), ("parts", ctypes.c_int64)]
+
+
+class SrgnnArgs(ctypes.Structure):
+    """mrec_srgnn_args (include/mrec.h, ABI 46): one description for both directions."""
+    _fields_ = ([("rows", ctypes.c_void_p), ("ld_rows", ctypes.c_int64),
+                 ("his", ctypes.c_void_p), ("ld_his", ctypes.c_int64)]
+                + [(n, ctypes.c_void_p) for n in
+                   ("w_ein", "w_eout", "w_ih", "w_hh", "w1", "w2", "wt", "b_ein", "b_eout", "b_iah",
+                    "b_oah", "b_ih", "b_hh", "c1", "q", "bt")]
+                + [("batch", ctypes.c_int64), ("L", ctypes.c_int32), ("D", ctypes.c_int32),
+                   ("steps", ctypes.c_int32), ("v", ctypes.c_void_p), ("hs", ctypes.c_void_p),
+                   ("dv", ctypes.c_void_p), ("d_rows", ctypes.c_void_p), ("ld_drows", ctypes.c_int64),
+                   ("part", ctypes.c_void_p), ("parts", ctypes.c_int64)])
 
 
 class GruArgs(ctypes.Structure):
@@ -635,6 +648,11 @@ SIGNATURES = {
     "mrec_mind_parts": (ctypes.c_int64, [_i64]),
     "mrec_mind_fwd": (ctypes.c_int, [ctypes.POINTER(MindArgs), _vp]),
     "mrec_mind_bwd": (ctypes.c_int, [ctypes.POINTER(MindArgs), _vp]),
+    "mrec_srgnn_supported": (ctypes.c_int32, [_i32, _i32, _i32]),
+    "mrec_srgnn_parts": (ctypes.c_int64, [_i64]),
+    "mrec_srgnn_param_count": (ctypes.c_int64, [_i32]),
+    "mrec_srgnn_fwd": (ctypes.c_int, [ctypes.POINTER(SrgnnArgs), _vp]),
+    "mrec_srgnn_bwd": (ctypes.c_int, [ctypes.POINTER(SrgnnArgs), _vp]),
     "mrec_graph_prop_supported": (ctypes.c_int32, [_i32, ctypes.c_int, ctypes.c_int]),
     "mrec_graph_long_row": (ctypes.c_int32, []),
     "mrec_graph_prop": (ctypes.c_int, [ctypes.POINTER(GraphPropArgs), _vp]),

@@ -11,7 +11,8 @@ numpy.  ``sasrec_encode`` is the SASRec encoder in torch ops: the CPU path, and 
 the layered path for the shapes and modes the fused kernels do not cover
 (``dense.sasrec_encode`` decides); ``hstu_encode`` is the same for the HSTU encoder
 (``dense.hstu_encode`` decides), ``mind_route`` for MIND's capsule routing
-(``dense.mind_route`` decides) and ``gru_encode`` for the GRU4Rec recurrence
+(``dense.mind_route`` decides), ``srgnn_encode`` for SR-GNN's session-graph encoder
+(``dense.srgnn_encode`` decides) and ``gru_encode`` for the GRU4Rec recurrence
 (``dense.gru_encode`` decides).  ``topk`` is ``mrec_topk``, the full-catalogue retrieval, in
 torch ops, chunked over the items (``retrieval.topk`` decides).  ``shared_negative_loss`` is
 ``mrec_shneg_loss_fwd`` / ``_bwd``, the list-wise losses over a shared pool of negatives, in
@@ -306,6 +307,85 @@ def mind_route(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor, rou
         if not last:
             b = b + torch.bmm(r(u.detach()), hd.transpose(1, 2))
     return u
+
+
+def srgnn_graph(his: torch.Tensor):
+    """The session graphs of a padded history in position space, tensor ops only ->
+    (valid [B, L] bool, alias [B, L] int64 (0 at invalid positions), rep [B, L] bool,
+    adj [B, L, L] fp32 binary).  valid_j = his_j > 0 or j == 0; alias(j) is the first valid
+    position with the id of j; rep marks the positions that are their own alias (the nodes);
+    adj[a, b] = 1 when two consecutive valid positions have the aliases a and b."""
+    B, L = his.shape
+    dev = his.device
+    valid = his > 0
+    valid[:, 0] = True
+    j = torch.arange(L, device=dev)
+    both = valid[:, :, None] & valid[:, None, :]
+    same = (his[:, :, None] == his[:, None, :]) & both
+    alias = torch.where(same, j[None, None, :], L).min(dim=-1).values
+    rep = valid & (alias == j)
+    alias = torch.where(valid, alias, torch.zeros_like(alias))
+    later = valid[:, None, :] & (j[None, None, :] > j[None, :, None])
+    nxt = torch.where(later, j[None, None, :], L).min(dim=-1).values
+    has = valid & (nxt < L)
+    dst = alias.gather(1, nxt.clamp(max=L - 1))
+    # edges of positions without a successor go to a spare column that is dropped
+    flat = torch.where(has, alias * L + dst, torch.full_like(alias, L * L))
+    adj = torch.zeros(B, L * L + 1, dtype=torch.float32, device=dev)
+    adj.scatter_(1, flat, 1.0)
+    return valid, alias, rep, adj[:, :L * L].reshape(B, L, L)
+
+
+def srgnn_encode(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor, w_ein, b_ein,
+                 w_eout, b_eout, b_iah, b_oah, w_ih, b_ih, w_hh, b_hh, w1, w2, c1, q, wt, bt,
+                 steps: int, rnd=None) -> torch.Tensor:
+    """The SR-GNN encoder (Wu et al., AAAI 2019) in fp32 torch ops, in position space;
+    autograd is its backward.
+
+    rows [B, L, D] item rows of the padded history, his [B, L] ids (``his_len`` is not
+    needed: validity is the ids') -> v [B, D].  With the graph of ``srgnn_graph``, H_a the row
+    at representative a and a zero row elsewhere, ``steps`` times
+        M_in = A_in (H W_ein^T + b_ein) + b_iah,  M_out = A_out (H W_eout^T + b_eout) + b_oah
+        gi = [M_in | M_out] W_ih^T + b_ih,  gh = H W_hh^T + b_hh
+        r = s(gi_r + gh_r), z = s(gi_z + gh_z), c = tanh(gi_c + r gh_c), H <- c + z (H - c)
+    (A_in X)_b = 1/indeg(b) sum_{a->b} X_a, (A_out X)_a = 1/outdeg(a) sum_{a->b} X_b, a degree
+    of 0 dividing as 1; then over the valid positions k, H_k = H[alias(k)] and h_last that of
+    the last one:  alpha_k = q . s(W1 h_last + W2 H_k + c1), g = sum_k alpha_k H_k,
+    v = Wt [g | h_last] + bt.
+
+    ``rnd`` rounds X, the six matrices of the products on H and M, the edge projections, M
+    and each step's H (identity here; ``bf16_round`` on a GPU, where this is the layered path
+    whose rounding points are the fused kernel's); Wt and g stay fp32."""
+    r_ = rnd if rnd is not None else (lambda t: t)
+    B, L, D = rows.shape
+    valid, alias, rep, adj = srgnn_graph(his)
+    s_in = 1.0 / adj.sum(1).clamp(min=1.0).unsqueeze(-1)   # [B, L, 1]: per target b
+    s_out = 1.0 / adj.sum(2).clamp(min=1.0).unsqueeze(-1)  # per source a
+    adj_t = adj.transpose(1, 2)
+    zero = torch.zeros((), dtype=torch.float32, device=rows.device)
+    h = torch.where(rep.unsqueeze(-1), r_(rows.float()), zero)
+    w_ein, w_eout, w_ih, w_hh, w1, w2 = (r_(w.float()) for w in (w_ein, w_eout, w_ih, w_hh, w1, w2))
+    for _ in range(int(steps)):
+        e_in = r_(h @ w_ein.t() + b_ein.float())
+        e_out = r_(h @ w_eout.t() + b_eout.float())
+        m = r_(torch.cat([torch.bmm(adj_t, e_in) * s_in + b_iah.float(),
+                          torch.bmm(adj, e_out) * s_out + b_oah.float()], dim=-1))
+        gi = m @ w_ih.t() + b_ih.float()
+        gh = h @ w_hh.t() + b_hh.float()
+        ir, iz, ic = gi.split(D, dim=-1)
+        hr, hz, hc = gh.split(D, dim=-1)
+        r = torch.sigmoid(ir + hr)
+        z = torch.sigmoid(iz + hz)
+        c = torch.tanh(ic + r * hc)
+        h = r_(c + z * (h - c))
+    hk = h.gather(1, alias.unsqueeze(-1).expand(B, L, D))  # the node's row at every position
+    j = torch.arange(L, device=rows.device)
+    last = (valid.long() * j).max(dim=1).values
+    h_last = hk[torch.arange(B, device=rows.device), last]
+    pre = (h_last @ w1.t() + c1.float()).unsqueeze(1) + hk @ w2.t()
+    alpha = (torch.sigmoid(pre) * q.float()).sum(-1) * valid.float()
+    g = (alpha.unsqueeze(-1) * hk).sum(1)
+    return torch.cat([g, h_last], dim=-1) @ wt.float().t() + bt.float()
 
 
 def gru_encode(rows: torch.Tensor, his_len: torch.Tensor, w_ih, w_hh, b_ih, b_hh,

@@ -1261,6 +1261,86 @@ def mind_route(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor,
                                rnd=cpu_path.bf16_round if rows.is_cuda else None)
 
 
+# the fused SR-GNN encoder (mrec_srgnn_*, srgnn.hip) is the default for the compiled shapes;
+# False selects the layered path (the parity tests set it)
+SRGNN_FUSED = True
+
+
+def srgnn_supported(D: int, L: int, steps: int) -> bool:
+    """True when the fused encoder covers this shape: D in {16, 32, 64}, L <= 64 and 1 to 4
+    GNN steps.  Decided from the shape alone; never an error."""
+    return bool(_mrec.lib().mrec_srgnn_supported(int(D), int(L), int(steps)))
+
+
+def _srgnn_params(model):
+    """In the order of the kernel's partial."""
+    return (model.W_ein, model.W_eout, model.W_ih, model.W_hh, model.W1, model.W2, model.Wt,
+            model.b_ein, model.b_eout, model.b_iah, model.b_oah, model.b_ih, model.b_hh, model.c1,
+            model.q, model.bt)
+
+
+class _SrgnnFn(torch.autograd.Function):
+    """The whole SR-GNN encoder over the gathered history rows [B, L, D]: one forward launch
+    (graph, every step, readout -> v [B, D]; H after each step saved when a gradient is
+    recorded), one backward launch (the rows' bf16 gradient + per-workgroup partials of the
+    sixteen dense gradients) and the partials' fixed-order sum."""
+
+    @staticmethod
+    def forward(ctx, rows, his, steps: int, save: bool, *params):
+        B, L, D = rows.shape
+        dev = rows.device
+        rows2 = _bf16_rows(rows.reshape(B * L, D))
+        his = his.to(torch.int32)
+        if his.stride(1) != 1:
+            his = his.contiguous()
+        ws = [_f32c(t) for t in params]
+        hs = torch.empty(steps, B, L, D, dtype=_BF16, device=dev) if save else None
+        v = torch.empty(B, D, dtype=torch.float32, device=dev)
+        a = _mrec.SrgnnArgs(rows2.data_ptr(), rows2.stride(0), his.data_ptr(), his.stride(0),
+                            *(w.data_ptr() for w in ws), B, L, D, int(steps), v.data_ptr(),
+                            _mrec.ptr(hs), None, None, 0, None, 0)
+        if B:
+            _mrec.call("mrec_srgnn_fwd", ctypes.byref(a), _mrec.stream_handle())
+        ctx.args, ctx.keep, ctx.params = a, (rows2, his, ws, hs), params
+        return v
+
+    @staticmethod
+    def backward(ctx, dv):
+        a, (rows2, his, ws, hs), params = ctx.args, ctx.keep, ctx.params
+        B, L, D = int(a.batch), int(a.L), int(a.D)
+        dev = rows2.device
+        dv = dv.detach().float().contiguous()
+        d_rows = torch.empty(B * L, D, dtype=_BF16, device=dev)
+        a.dv, a.d_rows, a.ld_drows = dv.data_ptr(), d_rows.data_ptr(), d_rows.stride(0)
+        lib = _mrec.lib()
+        grads = _sum_partials("mrec_srgnn_bwd", a, B, int(lib.mrec_srgnn_parts(B)),
+                              int(lib.mrec_srgnn_param_count(D)), [w.numel() for w in ws], params, dev)
+        ctx.args = ctx.keep = None
+        return (d_rows.reshape(B, L, D), None, None, None) + grads
+
+
+def srgnn_encode(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor,
+                 model) -> torch.Tensor:
+    """v [B, D] (fp32) of the SR-GNN encoder over the gathered history rows [B, L, D] with
+    ``model``'s sixteen parameters and ``gnn_steps`` (model/SRGNN.py).  On a GPU the fused
+    kernels when they cover the shape and the parameters are fp32; else, and on the CPU, the
+    layered path: the same arithmetic as torch ops (``cpu_path.srgnn_encode``), rounding to
+    bf16 on a GPU where the kernel does."""
+    from pytorchrec_amd import cpu_path
+    B, L, D = rows.shape
+    params = _srgnn_params(model)
+    steps = int(model.gnn_steps)
+    if (rows.is_cuda and SRGNN_FUSED and srgnn_supported(D, L, steps)
+            and all(p.dtype == torch.float32 for p in params)):
+        save = torch.is_grad_enabled() and (rows.requires_grad or any(p.requires_grad for p in params))
+        return _SrgnnFn.apply(rows, his, steps, save, *params)
+    m = model
+    return cpu_path.srgnn_encode(rows, his, his_len, m.W_ein, m.b_ein, m.W_eout, m.b_eout, m.b_iah,
+                                 m.b_oah, m.W_ih, m.b_ih, m.W_hh, m.b_hh, m.W1, m.W2, m.c1, m.q,
+                                 m.Wt, m.bt, steps,
+                                 rnd=cpu_path.bf16_round if rows.is_cuda else None)
+
+
 # the fused GRU4Rec encoder (mrec_gru_*, gru.hip) is the default for the compiled shapes;
 # False selects the layered path (the parity tests set it)
 GRU_FUSED = True
