@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MREC_ABI_VERSION 46
+#define MREC_ABI_VERSION 47
 #define MREC_MAX_TABLES 64      /* tables per table bank / per call */
 #define MREC_BWD_MAX_BATCH 8192  /* lookups per table per plan/apply call */
 #define MREC_BWD_HASH_MAX_BATCH 4096  /* batches up to this use the hash plan */
@@ -2596,6 +2596,82 @@ int64_t mrec_srgnn_parts(int64_t batch);
 int64_t mrec_srgnn_param_count(int32_t D);
 mrec_status mrec_srgnn_fwd(const mrec_srgnn_args *args, mrec_stream stream);
 mrec_status mrec_srgnn_bwd(const mrec_srgnn_args *args, mrec_stream stream);
+
+/* ------------------------------------------------------------------------- */
+/* Caser convolutional sequence encoder, fused, one launch each way (ABI 47; csrc/caser.hip) */
+/* ------------------------------------------------------------------------- */
+/*
+ * The horizontal and vertical convolutions, the max-over-time pooling and the final layer of
+ * Caser (Tang & Wang, WSDM 2018), one launch each way for the batch.  Per sample b, with
+ * valid_j = his[b, j] > 0 or j == 0, positions ascending in time, n = 1 + the last valid
+ * position and X the rows, read as zero at invalid positions and at and past n:
+ *   for each height h = heights[i] and filter f < n_h:
+ *     pre_h[t, f] = bh_h[f] + sum_{k < h, d} X[t + k, d] wh_h[f, k, d],  t = 0 .. max(n - h, 0)
+ *     pick_h[f]   = the lowest t that attains max_t pre_h[t, f];  o_h[f] = relu(pre_h[pick, f])
+ *   for each vertical filter j < n_v, indexed by the distance from the last item:
+ *     o_v[j, d]   = relu(bv[j] + sum_{t < n} wv[j, n - 1 - t] X[t, d])
+ *   z = bf16([o_h for each height | o_v flattened]), Z = n_heights n_h + n_v D
+ *   v = relu(w1 z + b1).
+ * bf16 MFMA operands (X, z, and wh, wv, w1 rounded from their fp32 masters in the kernel),
+ * fp32 accumulation, biases, pooling and relu.
+ *   rows, his: as mrec_sasrec_args (bf16 rows, 16-byte aligned);
+ *   wh[i] [n_h, heights[i], D], w1 [D, Z]: contiguous fp32, 16-byte aligned; bh[i] [n_h],
+ *   wv [n_v, L], bv [n_v], b1 [D]: contiguous fp32;
+ *   v [batch, D] fp32, contiguous: written by the forward, read by the backward;
+ *   z [batch, Z] bf16 (16-byte aligned) and pick [batch, n_heights n_h] uint8: written by the
+ *   forward when not NULL (both or neither; NULL: a forward that nobody differentiates) and read
+ *   by the backward, which recomputes no convolution;
+ *   dv [batch, D] fp32; dpre [batch, D] bf16, written by the backward: dv where v > 0, else 0,
+ *   so that dw1 = dpre^T z and db1 = dpre^T 1 are one product over the batch for the caller
+ *   (mrec_gemm with a ones column);
+ *   d_rows (row stride ld_drows) the rows' bf16 gradient, bitwise zero at invalid positions;
+ *   part [parts][mrec_caser_param_count(..)] fp32 per-workgroup partials of the other dense
+ *   gradients in the order wh[0..], bh[0..], wv, bv (parts = mrec_caser_parts(batch)), to be
+ *   summed in workgroup order by mrec_sasrec_wgrad.  The backward rounds dpre and the pooled
+ *   gradients of the data side to bf16 as MFMA operands; the weight gradients take them in fp32.
+ * One description for both directions; the forward ignores the backward's fields.  No
+ * atomics, and a sample's v, pick and d_rows depend on that sample alone: two runs, and two
+ * batch orders, give equal bits.  Compiled shapes (mrec_caser_supported): D in {16, 32, 64},
+ * 1 <= L <= 64, 1 to 4 distinct ascending heights in 1..8, n_h 16 or 32, 1 <= n_v <= 8 and
+ * (sum of heights) n_h D <= 16384; anything else is MREC_EINVAL before any device work.
+ * Stream-ordered, no allocation.
+ */
+typedef struct {
+  const void *rows;
+  int64_t ld_rows;
+  const int32_t *his;
+  int64_t ld_his;
+  const float *wh[4];
+  const float *bh[4];
+  const float *wv;
+  const float *bv;
+  const float *w1;
+  const float *b1;
+  int64_t batch;
+  int32_t L;
+  int32_t D;
+  int32_t n_heights;
+  int32_t heights[4];
+  int32_t n_h;
+  int32_t n_v;
+  float *v;
+  void *z;
+  uint8_t *pick;
+  const float *dv;
+  void *dpre;
+  void *d_rows;
+  int64_t ld_drows;
+  float *part;
+  int64_t parts;
+} mrec_caser_args;
+
+int32_t mrec_caser_supported(int32_t D, int32_t L, int32_t n_heights, const int32_t *heights,
+                             int32_t n_h, int32_t n_v);
+int64_t mrec_caser_parts(int64_t batch);
+int64_t mrec_caser_param_count(int32_t D, int32_t L, int32_t n_heights, const int32_t *heights,
+                               int32_t n_h, int32_t n_v);
+mrec_status mrec_caser_fwd(const mrec_caser_args *args, mrec_stream stream);
+mrec_status mrec_caser_bwd(const mrec_caser_args *args, mrec_stream stream);
 
 #ifdef __cplusplus
 }

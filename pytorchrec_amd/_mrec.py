@@ -20,7 +20,7 @@ import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("MREC_LIB_PATH") or os.path.join(LIB_DIR, "libmrec.so")
 
-ABI_VERSION = 46
+ABI_VERSION = 47
 MAX_TABLES = 64
 BWD_MAX_BATCH = 8192
 BWD_HASH_MAX_BATCH = 4096  # batches up to this use the hash plan (fusable into a GEMM launch)
@@ -293,6 +293,20 @@ class SrgnnArgs(ctypes.Structure):
                    ("steps", ctypes.c_int32), ("v", ctypes.c_void_p), ("hs", ctypes.c_void_p),
                    ("dv", ctypes.c_void_p), ("d_rows", ctypes.c_void_p), ("ld_drows", ctypes.c_int64),
                    ("part", ctypes.c_void_p), ("parts", ctypes.c_int64)])
+
+
+class CaserArgs(ctypes.Structure):
+    """mrec_caser_args (include/mrec.h, ABI 47): one description for both directions."""
+    _fields_ = [("rows", ctypes.c_void_p), ("ld_rows", ctypes.c_int64),
+                ("his", ctypes.c_void_p), ("ld_his", ctypes.c_int64),
+                ("wh", ctypes.c_void_p * 4), ("bh", ctypes.c_void_p * 4),
+                ("wv", ctypes.c_void_p), ("bv", ctypes.c_void_p), ("w1", ctypes.c_void_p),
+                ("b1", ctypes.c_void_p), ("batch", ctypes.c_int64), ("L", ctypes.c_int32),
+                ("D", ctypes.c_int32), ("n_heights", ctypes.c_int32), ("heights", ctypes.c_int32 * 4),
+                ("n_h", ctypes.c_int32), ("n_v", ctypes.c_int32), ("v", ctypes.c_void_p),
+                ("z", ctypes.c_void_p), ("pick", ctypes.c_void_p), ("dv", ctypes.c_void_p),
+                ("dpre", ctypes.c_void_p), ("d_rows", ctypes.c_void_p), ("ld_drows", ctypes.c_int64),
+                ("part", ctypes.c_void_p), ("parts", ctypes.c_int64)]
 
 
 class GruArgs(ctypes.Structure):
@@ -653,6 +667,11 @@ SIGNATURES = {
     "mrec_srgnn_param_count": (ctypes.c_int64, [_i32]),
     "mrec_srgnn_fwd": (ctypes.c_int, [ctypes.POINTER(SrgnnArgs), _vp]),
     "mrec_srgnn_bwd": (ctypes.c_int, [ctypes.POINTER(SrgnnArgs), _vp]),
+    "mrec_caser_supported": (ctypes.c_int32, [_i32, _i32, _i32, ctypes.POINTER(ctypes.c_int32), _i32, _i32]),
+    "mrec_caser_parts": (ctypes.c_int64, [_i64]),
+    "mrec_caser_param_count": (ctypes.c_int64, [_i32, _i32, _i32, ctypes.POINTER(ctypes.c_int32), _i32, _i32]),
+    "mrec_caser_fwd": (ctypes.c_int, [ctypes.POINTER(CaserArgs), _vp]),
+    "mrec_caser_bwd": (ctypes.c_int, [ctypes.POINTER(CaserArgs), _vp]),
     "mrec_graph_prop_supported": (ctypes.c_int32, [_i32, ctypes.c_int, ctypes.c_int]),
     "mrec_graph_long_row": (ctypes.c_int32, []),
     "mrec_graph_prop": (ctypes.c_int, [ctypes.POINTER(GraphPropArgs), _vp]),

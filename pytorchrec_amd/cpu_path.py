@@ -12,7 +12,8 @@ the layered path for the shapes and modes the fused kernels do not cover
 (``dense.sasrec_encode`` decides); ``hstu_encode`` is the same for the HSTU encoder
 (``dense.hstu_encode`` decides), ``mind_route`` for MIND's capsule routing
 (``dense.mind_route`` decides), ``srgnn_encode`` for SR-GNN's session-graph encoder
-(``dense.srgnn_encode`` decides) and ``gru_encode`` for the GRU4Rec recurrence
+(``dense.srgnn_encode`` decides), ``caser_encode`` for Caser's convolutional encoder
+(``dense.caser_encode`` decides) and ``gru_encode`` for the GRU4Rec recurrence
 (``dense.gru_encode`` decides).  ``topk`` is ``mrec_topk``, the full-catalogue retrieval, in
 torch ops, chunked over the items (``retrieval.topk`` decides).  ``shared_negative_loss`` is
 ``mrec_shneg_loss_fwd`` / ``_bwd``, the list-wise losses over a shared pool of negatives, in
@@ -386,6 +387,55 @@ def srgnn_encode(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor, w
     alpha = (torch.sigmoid(pre) * q.float()).sum(-1) * valid.float()
     g = (alpha.unsqueeze(-1) * hk).sum(1)
     return torch.cat([g, h_last], dim=-1) @ wt.float().t() + bt.float()
+
+
+def caser_encode(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor, whs, bhs, wv, bv,
+                 w1, b1, heights, dropout: float = 0.0, training: bool = False, rnd=None,
+                 return_pick: bool = False):
+    """The Caser encoder (Tang & Wang, WSDM 2018) in fp32 torch ops; autograd is its backward.
+
+    rows [B, L, D] item rows of the padded history, his [B, L] ids (``his_len`` is not needed:
+    validity is the ids'), whs[i] [n_h, heights[i], D], bhs[i] [n_h], wv [n_v, L], bv [n_v],
+    w1 [D, Z], b1 [D] -> v [B, D], and with ``return_pick`` also pick [B, len(heights) n_h]
+    (int64).  With valid_j = his_j > 0 or j == 0, n = 1 + the last valid position and X the
+    rows, zero at invalid positions:
+        pre_h[t, f] = bh_h[f] + sum_{k < h, d} X[t + k, d] Wh_h[f, k, d],  t = 0 .. max(n - h, 0)
+                      (rows at or past n read as 0: a history shorter than h has the window t = 0)
+        pick_h[f]   = the lowest t that attains max_t pre_h[t, f];  o_h[f] = relu(pre_h[pick, f])
+        o_v[j, d]   = relu(bv[j] + sum_{t < n} Wv[j, n - 1 - t] X[t, d])
+        z = [o_h for each height | o_v flattened],  v = relu(W1 dropout(z) + b1)
+    The pooled gradient goes to the picked window alone.
+
+    ``rnd`` rounds X, Wh, Wv, W1 and z (identity here; ``bf16_round`` on a GPU, where this is
+    the layered path whose rounding points are the fused kernel's)."""
+    r_ = rnd if rnd is not None else (lambda t: t)
+    B, L, D = rows.shape
+    dev = rows.device
+    valid = his > 0
+    valid[:, 0] = True
+    j = torch.arange(L, device=dev)
+    n = (valid.long() * (j + 1)).max(dim=1).values  # [B]
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    x = torch.where(valid.unsqueeze(-1), r_(rows.float()), zero)
+    outs, picks = [], []
+    for h, wh, bh in zip(heights, whs, bhs):
+        win = torch.nn.functional.pad(x, (0, 0, 0, h - 1)).unfold(1, h, 1)  # [B, L, D, h]
+        pre = torch.einsum("btdk,fkd->btf", win, r_(wh.float())) + bh.float()
+        inside = j[None, :] <= (n - h).clamp(min=0)[:, None]  # [B, L]
+        masked = torch.where(inside.unsqueeze(-1), pre.detach(), zero - float("inf"))
+        top = masked.max(dim=1, keepdim=True).values
+        # the tie rule, explicitly: the lowest window that attains the maximum
+        pick = torch.where(masked == top, j[None, :, None], L - 1).min(dim=1).values  # [B, n_h]
+        outs.append(torch.relu(pre.gather(1, pick.unsqueeze(1)).squeeze(1)))
+        picks.append(pick)
+    dist = n[:, None] - 1 - j[None, :]  # [B, L]: distance from the last item
+    wvr = r_(wv.float())[:, dist.clamp(min=0)] * (dist >= 0).float()  # [n_v, B, L]
+    o_v = torch.relu(torch.einsum("jbt,btd->bjd", wvr, x) + bv.float()[None, :, None])
+    z = r_(torch.cat(outs + [o_v.reshape(B, -1)], dim=-1))
+    if training and dropout > 0:
+        z = torch.nn.functional.dropout(z, dropout, True)
+    v = torch.relu(z @ r_(w1.float()).t() + b1.float())
+    return (v, torch.cat(picks, dim=-1)) if return_pick else v
 
 
 def gru_encode(rows: torch.Tensor, his_len: torch.Tensor, w_ih, w_hh, b_ih, b_hh,

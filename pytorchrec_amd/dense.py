@@ -1341,6 +1341,119 @@ def srgnn_encode(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor,
                                  rnd=cpu_path.bf16_round if rows.is_cuda else None)
 
 
+# the fused Caser encoder (mrec_caser_*, caser.hip) is the default for the compiled shapes;
+# False selects the layered path (the parity tests set it)
+CASER_FUSED = True
+
+
+def _caser_heights(heights):
+    return (ctypes.c_int32 * 4)(*heights) if 1 <= len(heights) <= 4 else None
+
+
+def caser_supported(D: int, L: int, heights, n_h: int, n_v: int, dropout: float = 0.0,
+                    training: bool = False) -> bool:
+    """True when the fused encoder covers this shape: D in {16, 32, 64}, L <= 64, 1 to 4
+    distinct ascending heights in 1..8, n_h 16 or 32, n_v 1..8, (sum of heights) n_h D <= 16384
+    and no active dropout.  Decided from the shape alone; never an error."""
+    hts = _caser_heights(tuple(int(h) for h in heights))
+    if hts is None or (training and dropout > 0):
+        return False
+    return bool(_mrec.lib().mrec_caser_supported(int(D), int(L), len(heights), hts, int(n_h), int(n_v)))
+
+
+def _caser_params(model):
+    """In the order of the kernel's partial, then the final layer's pair."""
+    return (tuple(getattr(model, f"Wh_{h}") for h in model.heights)
+            + tuple(getattr(model, f"bh_{h}") for h in model.heights)
+            + (model.Wv, model.bv, model.W1, model.b1))
+
+
+class _CaserFn(torch.autograd.Function):
+    """The whole Caser encoder over the gathered history rows [B, L, D]: one forward launch
+    (both convolutions, the pooling, the final layer -> v [B, D]; z and pick saved when a
+    gradient is recorded or the pick is asked for), one backward launch (the rows' bf16
+    gradient, per-workgroup partials of the convolutions' dense gradients and the bf16 dpre),
+    the partials' fixed-order sum, and dW1, db1 = dpre^T [z | 1] as one GEMM over the batch."""
+
+    @staticmethod
+    def forward(ctx, rows, his, heights, n_h: int, n_v: int, save: bool, *params):
+        B, L, D = rows.shape
+        dev = rows.device
+        nH = len(heights)
+        Z = nH * n_h + n_v * D
+        rows2 = _bf16_rows(rows.reshape(B * L, D))
+        his = his.to(torch.int32)
+        if his.stride(1) != 1:
+            his = his.contiguous()
+        ws = [_f32c(t) for t in params]
+        z = torch.empty(B, Z, dtype=_BF16, device=dev) if save else None
+        pick = torch.empty(B, nH * n_h, dtype=torch.uint8, device=dev) if save else None
+        v = torch.empty(B, D, dtype=torch.float32, device=dev)
+        a = _mrec.CaserArgs()
+        a.rows, a.ld_rows, a.his, a.ld_his = rows2.data_ptr(), rows2.stride(0), his.data_ptr(), his.stride(0)
+        for i in range(nH):
+            a.wh[i], a.bh[i], a.heights[i] = ws[i].data_ptr(), ws[nH + i].data_ptr(), heights[i]
+        a.wv, a.bv, a.w1, a.b1 = (w.data_ptr() for w in ws[2 * nH:])
+        a.batch, a.L, a.D, a.n_heights, a.n_h, a.n_v = B, L, D, nH, n_h, n_v
+        a.v, a.z, a.pick = v.data_ptr(), _mrec.ptr(z), _mrec.ptr(pick)
+        if B:
+            _mrec.call("mrec_caser_fwd", ctypes.byref(a), _mrec.stream_handle())
+        ctx.args, ctx.keep, ctx.params = a, (rows2, his, ws, v, z, pick), params
+        out_pick = pick if save else torch.empty(0, dtype=torch.uint8, device=dev)
+        ctx.mark_non_differentiable(out_pick)
+        return v, out_pick
+
+    @staticmethod
+    def backward(ctx, dv, _dpick):
+        a, (rows2, his, ws, v, z, pick), params = ctx.args, ctx.keep, ctx.params
+        B, L, D, nH = int(a.batch), int(a.L), int(a.D), int(a.n_heights)
+        dev = rows2.device
+        dv = dv.detach().float().contiguous()
+        d_rows = torch.empty(B * L, D, dtype=_BF16, device=dev)
+        dpre = torch.empty(B, D, dtype=_BF16, device=dev)
+        a.dv, a.dpre, a.d_rows, a.ld_drows = dv.data_ptr(), dpre.data_ptr(), d_rows.data_ptr(), d_rows.stride(0)
+        lib = _mrec.lib()
+        P = int(lib.mrec_caser_param_count(D, L, nH, a.heights, int(a.n_h), int(a.n_v)))
+        grads = _sum_partials("mrec_caser_bwd", a, B, int(lib.mrec_caser_parts(B)), P,
+                              [w.numel() for w in ws[:-2]], params[:-2], dev)
+        W1, b1 = params[-2:]
+        dest = _grad_dest(W1, b1, None, "rowtr", decided=(None, dp_grads(W1, b1)))
+        if B:  # dW1[d, zi] = sum_b dpre[b, d] z[b, zi], db1 through the ones column
+            gemm(dpre, _mrec.LAYOUT_COL, z, _mrec.LAYOUT_COL, D, z.shape[1], B, **dest.kw)
+        else:
+            dest.kw["out"].zero_()
+            dest.kw["ones_out"].zero_()
+        ctx.args = ctx.keep = None
+        return (d_rows.reshape(B, L, D), None, None, None, None, None) + grads + (dest.dW, dest.db)
+
+
+def caser_encode(rows: torch.Tensor, his: torch.Tensor, his_len: torch.Tensor, model,
+                 return_pick: bool = False):
+    """v [B, D] (fp32) of the Caser encoder over the gathered history rows [B, L, D] with
+    ``model``'s parameters, ``heights``, ``n_h``, ``n_v`` and ``dropout`` (model/Caser.py); with
+    ``return_pick`` also the pooled windows [B, len(heights) n_h].  On a GPU the fused kernels
+    when they cover the shape, the parameters are fp32 and no dropout is active; else, and on
+    the CPU, the layered path: the same arithmetic as torch ops (``cpu_path.caser_encode``),
+    rounding to bf16 on a GPU where the kernel does."""
+    from pytorchrec_amd import cpu_path
+    B, L, D = rows.shape
+    params = _caser_params(model)
+    heights, n_h, n_v = tuple(model.heights), int(model.n_h), int(model.n_v)
+    if (rows.is_cuda and CASER_FUSED
+            and caser_supported(D, L, heights, n_h, n_v, model.dropout, model.training)
+            and all(p.dtype == torch.float32 for p in params)):
+        save = return_pick or (torch.is_grad_enabled()
+                               and (rows.requires_grad or any(p.requires_grad for p in params)))
+        v, pick = _CaserFn.apply(rows, his, heights, n_h, n_v, save, *params)
+        return (v, pick) if return_pick else v
+    nH = len(heights)
+    return cpu_path.caser_encode(rows, his, his_len, params[:nH], params[nH:2 * nH], model.Wv,
+                                 model.bv, model.W1, model.b1, heights, dropout=model.dropout,
+                                 training=model.training,
+                                 rnd=cpu_path.bf16_round if rows.is_cuda else None,
+                                 return_pick=return_pick)
+
+
 # the fused GRU4Rec encoder (mrec_gru_*, gru.hip) is the default for the compiled shapes;
 # False selects the layered path (the parity tests set it)
 GRU_FUSED = True

@@ -14,6 +14,7 @@ from pytorchrec_amd.model.GRU4Rec import GRU4Rec
 from pytorchrec_amd.model.HSTU import HSTU
 from pytorchrec_amd.model.MIND import MIND
 from pytorchrec_amd.model.SRGNN import SRGNN
+from pytorchrec_amd.model.Caser import Caser
 from pytorchrec_amd.model.DIEN import DIEN
 from pytorchrec_amd.model.NCF import NCF
 from pytorchrec_amd.model.LightGCN import LightGCN

@@ -14,6 +14,7 @@ from pytorchrec_amd.model.IModel import IModel
 from pytorchrec_amd.model.LightGCN import LightGCN
 from pytorchrec_amd.model.MIND import MIND
 from pytorchrec_amd.model.SRGNN import SRGNN
+from pytorchrec_amd.model.Caser import Caser
 from pytorchrec_amd.model.NCF import NCF
 from pytorchrec_amd.model.SASRec import SASRec
 from pytorchrec_amd.model.SVDPP import SVDPP
@@ -28,6 +29,7 @@ _model_classes: Dict[str, Type[IModel]] = {
     "hstu": HSTU,
     "mind": MIND,
     "srgnn": SRGNN,
+    "caser": Caser,
     "ncf": NCF,
     "lightgcn": LightGCN,
     "fm": FM,
